@@ -119,6 +119,23 @@ def test_seeded_replay_names():
     assert bench.pmc_record_path("c5", "none", "stream").endswith("pmc_c5_stream.json")
 
 
+def test_dump_arrays_are_float32_or_float64(tmp_path):
+    """--dump-outputs files: narrow elements as float32, 4- and 8-byte ones as float64
+    (int32 and float64 exactly); ranks other than 0 keep their own files."""
+    import numpy as np
+    arrays = {"board": np.array([[0, 65535]], dtype=np.uint16),
+              "episode_length": np.array([2 ** 31 - 1], dtype=np.int32),
+              "reward": np.array([0.1], dtype=np.float64), "done": np.uint8(1)}
+    bench.write_arrays(str(tmp_path / "d"), 0, arrays)
+    bench.write_arrays(str(tmp_path / "d"), 1, {"done": np.uint8(0)})
+    got = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in arrays}
+    assert got["board"].dtype == np.float32 and got["board"].tolist() == [[0.0, 65535.0]]
+    assert got["episode_length"].dtype == np.float64 and got["episode_length"][0] == 2 ** 31 - 1
+    assert got["reward"].dtype == np.float64 and got["reward"][0] == 0.1
+    assert got["done"].dtype == np.float32 and got["done"] == 1.0
+    assert np.load(str(tmp_path / "d" / "done_rank1.npy")) == 0.0
+
+
 def test_c1_cpu_leg_single_level():
     """C1's CPU chain leg takes the single 25x25 level file (one env, one thread)."""
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--cpu-leg", json.dumps(

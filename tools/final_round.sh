@@ -21,9 +21,11 @@ if [ "$P" = a ]; then
   bash tools/profile.sh ${T}_c3p --obs packed || exit 1
   bash tools/profile.sh ${T}_c3ch --obs channels || exit 1
   bash tools/profile.sh ${T}_c3bf --obs channels --obs-dtype bfloat16 || exit 1
-  timeout -k 10 600 python3 bench.py --pmc off > gpurun_out/$T/bench.json 2> gpurun_out/$T/bench.err \
-      || { tail -20 gpurun_out/$T/bench.err; exit 1; }
-  cat gpurun_out/$T/bench.json
+  # (OUT_ROOT: the folder that collects the session's outputs)
+  OUT=${OUT_ROOT:-$R/out}/$T; mkdir -p $OUT
+  timeout -k 10 600 python3 bench.py --full --pmc off > $OUT/bench.json 2> $OUT/bench.err \
+      || { tail -20 $OUT/bench.err; exit 1; }
+  cat $OUT/bench.json
 else
   bash tools/profile.sh ${T}_c5 --config c5 || exit 1
   bash tools/profile.sh ${T}_c5s --config c5 --rng stream || exit 1

@@ -13,7 +13,9 @@ if [ -n "$K" ]; then KARG=(-k "$K"); else KARG=(); fi
 timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread "${KARG[@]}" \
     > gpurun_out/$TAG/pytest.log 2>&1 || { tail -40 gpurun_out/$TAG/pytest.log; exit 1; }
 tail -3 gpurun_out/$TAG/pytest.log
-timeout -k 10 900 python3 bench.py > gpurun_out/$TAG/bench.json 2> gpurun_out/$TAG/bench.err \
-    || { tail -20 gpurun_out/$TAG/bench.err; exit 1; }
-cat gpurun_out/$TAG/bench.json
+# (OUT_ROOT: the folder that collects the session's outputs)
+OUT=${OUT_ROOT:-$R/out}/$TAG; mkdir -p $OUT
+timeout -k 10 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err \
+    || { tail -20 $OUT/bench.err; exit 1; }
+cat $OUT/bench.json
 bash tools/profile.sh $TAG/prof || exit 1
