@@ -381,7 +381,10 @@ __device__ __forceinline__ int stream_draws(const u32 elig[2], u32 sp[2], double
 // one quantity at a time so only the reduced results stay live.
 // held (optional): the changed cells that held a bit of a plane other than 0, 3, 9-11
 // before the step (the planes a change clears but never sets), for plane-mode stores
-template <class Geo>
+// PIN (a kernel short of registers): the terms the new planes need are reduced before
+// the spawner phase; left alone the compiler sinks them past it as their ~40 partial
+// terms, which then stay live through the draws
+template <bool PIN = false, class Geo>
 __device__ __forceinline__ void rule_planes(u32 P[32], u32 chg[2], Geo &&g, const SpawnCtx &sc,
                                             u32 tensor, u32 *held = nullptr) {
     u32 eq3[2], eq34[2];
@@ -453,6 +456,10 @@ __device__ __forceinline__ void rule_planes(u32 P[32], u32 chg[2], Geo &&g, cons
 #pragma unroll
         for (int k = 0; k < 3; k++) colk[k][w] = two[1 + k][w];
         elig[w] = dead_ok & ~eq3[w] & any[2][w];
+        if (PIN) {
+            asm volatile("" : "+v"(kill[w]), "+v"(birth[w]), "+v"(pairD[w]), "+v"(elig[w]));
+            asm volatile("" : "+v"(colk[0][w]), "+v"(colk[1][w]), "+v"(colk[2][w]));
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- spawner phase: spawner colours reach every newborn; eligible cells draw

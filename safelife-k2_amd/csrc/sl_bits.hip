@@ -851,6 +851,14 @@ struct PlaneSlots {
 // the instantiations: every plane, the C3 / C4 pools' planes (cell bits 0-6, 8-10, 15),
 // and any other mask at run time
 constexpr u32 kKeepAll = 0xFFFFu, kKeepC3 = 0x877Fu;
+// the plane kernel's waves per SIMD: five (96 VGPRs; 20 x 8 KiB is the CU's LDS) where
+// the instantiation fits that budget without spills -- the C3 / C4 planes without views
+// (its 10 planes never held are 20 registers fewer); the others spill there (13-24
+// VGPRs) and stay at four
+constexpr int kMinWavesPlanes = 5;
+constexpr int planes_min_waves(u32 k16, int obs) {
+    return (obs == 0 && k16 == kKeepC3) ? kMinWavesPlanes : kMinWaves;
+}
 
 // the kept plane words of an env, DMA'd into the wave's buffer in their packed order
 // (position p of lane l at buf[p * 64 + l]); no registers held while they are in flight
@@ -906,7 +914,7 @@ __device__ __forceinline__ u32 lds_plane_cell(const lds_u32 *buf, PlaneSlots<K16
 // colours added into planes 12-14 (a bit-sliced adder, exact whatever the board's bits),
 // ONE transpose, the view-form rows into the buffer
 template <u32 K16, int OBS>
-__global__ void __launch_bounds__(64, kMinWaves)
+__global__ void __launch_bounds__(64, planes_min_waves(K16, OBS))
 k_env_step_bits64_planes(StepKArgs ka) {
     const sl_env_state &st = ka.st;
     const StepArgs &a = ka.a;
@@ -956,7 +964,7 @@ k_env_step_bits64_planes(StepKArgs ka) {
             transpose32(PG);
         }
         u32 cg[2];
-        rule_planes(PG, cg, Geo64<SPAWN_PHILOX>{lane, ssrc, 0, 0}, sc, 1u);
+        rule_planes<true>(PG, cg, Geo64<SPAWN_PHILOX>{lane, ssrc, 0, 0}, sc, 1u);
         const u32 rg = wave_or(cg[0] | cg[1]);
         const bool all = !(pok & 2);
 #pragma unroll
@@ -1026,6 +1034,9 @@ k_env_step_bits64_planes(StepKArgs ka) {
     for (int k = 0; k < 4; k++) {
         eidx[k] = __builtin_amdgcn_readfirstlane(eidx[k]);
         eval[k] = (u32)__builtin_amdgcn_readfirstlane((int)eval[k]);
+        // no cell of the batch holds a bit outside the kept planes (board_zero), an
+        // edited one included: said here, the planes not kept stay constants below
+        if (K16) eval[k] &= K16;
     }
     RecFields fl{V, __builtin_amdgcn_readfirstlane(env.go), __builtin_amdgcn_readfirstlane(env.ax),
                  __builtin_amdgcn_readfirstlane(env.ay), 0.0};
@@ -1048,6 +1059,10 @@ k_env_step_bits64_planes(StepKArgs ka) {
     // (a lane mask, not two words held through the scores: such a lane stores those
     // planes for every changed word)
     const uint64_t held_lanes = __ballot((held[0] | held[1]) != 0u);
+    // the new plane 3 is read by the stores alone: computed here, or the compiler sinks
+    // it into them and keeps the rule's pair terms (eight registers) through the scores
+#pragma unroll
+    for (int w = 0; w < 2; w++) asm volatile("" : "+v"(PL(PB, 3, w)));
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- scores over the new board and goals
@@ -1058,6 +1073,11 @@ k_env_step_bits64_planes(StepKArgs ka) {
     } else {
         read_pairs(buf, lane, PS);
         transpose32(PS);
+        // planes no board holds: no start board either (as pool_planes_lds has them), so
+        // neither path keeps a register for them
+#pragma unroll
+        for (int q = 0; q < 32; q++)
+            if (!((KEEP >> (q & 15)) & 1u)) PS[q] = 0u;
     }
     int pts, scr, pos, side;
     score_planes(PB, gcol, PS, &pts, &scr, &pos, &side);
