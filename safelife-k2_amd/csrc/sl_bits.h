@@ -1,5 +1,7 @@
 // sl_bits.h -- building blocks of the bit-sliced env-step kernels (sl_bits.hip for
-// 64x64 boards, sl_bits128.hip for 128x128 boards).
+// 64x64 boards, sl_bits_small.hip for boards up to 32 rows, sl_bits128.hip for 128x128
+// boards): the rule, the scores, the per-env record, and the step phases the kernels
+// run between them ("shared step phases" at the end).
 //
 // A lane holds two board columns over 32 rows as 16 bit planes x 2 words: plane k,
 // word w, bit y = bit k of cell(row0 + y, col0 + w) (PL(P, k, w) below).  The rule
@@ -28,16 +30,15 @@ typedef uint32_t u32;
 __device__ __forceinline__ u32 maj(u32 a, u32 b, u32 c) { return (a & b) | (c & (a | b)); }
 __device__ __forceinline__ u32 mux(u32 s, u32 a, u32 b) { return (s & a) | (~s & b); }
 
-// whole-wave lane rotations (wrap at 64 lanes); every lane has a source, so no old value
-__device__ __forceinline__ u32 lane_m1(u32 v) {      // value of lane l - 1
-    return (u32)__builtin_amdgcn_mov_dpp((int)v, 0x13C, 0xF, 0xF, false);  // wave_ror:1
+// v of the lane the DPP control CTRL names; every lane has a source, so no old value
+template <int CTRL>
+__device__ __forceinline__ u32 dpp(u32 v) {
+    return (u32)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, false);
 }
-__device__ __forceinline__ u32 lane_p1(u32 v) {      // value of lane l + 1
-    return (u32)__builtin_amdgcn_mov_dpp((int)v, 0x134, 0xF, 0xF, false);  // wave_rol:1
-}
-__device__ __forceinline__ u32 lane_x1(u32 v) {      // value of lane l ^ 1
-    return (u32)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-}
+// whole-wave lane rotations (wrap at 64 lanes)
+__device__ __forceinline__ u32 lane_m1(u32 v) { return dpp<0x13C>(v); }   // lane l - 1: wave_ror:1
+__device__ __forceinline__ u32 lane_p1(u32 v) { return dpp<0x134>(v); }   // lane l + 1: wave_rol:1
+__device__ __forceinline__ u32 lane_x1(u32 v) { return dpp<0xB1>(v); }    // lane l ^ 1: quad_perm [1,0,3,2]
 
 struct H3 {
     u32 l0, r1;          // column col0 - 1, column col0 + 2
@@ -96,11 +97,6 @@ template <int S>
 __device__ __forceinline__ void load_pairs_nt(const u32 *__restrict__ p, u32 D[32]) {
 #pragma unroll
     for (int y = 0; y < 32; y++) D[y] = __builtin_nontemporal_load(p + y * S);
-}
-
-template <int CTRL>
-__device__ __forceinline__ u32 dpp(u32 v) {
-    return (u32)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, false);
 }
 
 // Row masks (bit y) of the 64-byte sectors to write when lanes 16k .. 16k+15 hold
@@ -704,6 +700,85 @@ struct RecFields {
     __device__ int side_effect() const { return rec(V, R_SIDE); }
     __device__ double bonus(int) const { return bval; }
 };
+
+// ---------------------------------------------------------------- shared step phases
+// What every step kernel does the same way between its loads, the rule, the scores and
+// the epilogue.  Each is one straight-line piece: the kernels keep their own order,
+// waits and scheduling barriers around the calls.
+
+// the env's Philox key and spawn probability (spawn_bits: the record's R_SPAWN dword)
+__device__ __forceinline__ SpawnCtx spawn_ctx(const StepArgs &a, int64_t b, int spawn_bits) {
+    SpawnCtx sc;
+    sc.gid = a.env0 + (uint32_t)b;
+    sc.step = a.step;
+    sc.seed = a.seed;
+    set_spawn_prob(sc, __int_as_float(spawn_bits));
+    return sc;
+}
+
+// the supplied uniforms; replay (SPAWN_STREAM) adds the error word and the first uniform
+// of env b's board and goals (pos_b, pos_g) from the scratch words the prologue left
+template <int MODE>
+__device__ __forceinline__ StreamSrc stream_src(const StepArgs &a, int64_t *scratch, int64_t B,
+                                                int64_t b, int64_t &pos_b, int64_t &pos_g) {
+    StreamSrc src{a.draws, a.n_draws, nullptr, a.draw_mask, a.draw_bits};
+    pos_b = 0;
+    pos_g = 0;
+    if (MODE == SPAWN_STREAM) {
+        const Scratch w = scratch_of(scratch, B);
+        src.err = w.err;
+        pos_b = w.offsets[2 * b];
+        pos_g = w.offsets[2 * b + 1];
+    }
+    return src;
+}
+
+// the epilogue's record view with the post-action agent; the bonus-table entry it may
+// need is issued now, consumed by the epilogue
+__device__ __forceinline__ RecFields rec_fields(const StepArgs &a, u32 V, int go, int ax, int ay) {
+    RecFields fl{V, go, ax, ay, 0.0};
+    if (a.bonus_period > 0)
+        fl.bval = a.bonus_table[bonus_dist(fl.ax, fl.ay, fl.prior_x(fl.prior_head()),
+                                           fl.prior_y(fl.prior_head()), fl.prior_len(),
+                                           a.bonus_period, a.bonus_len)];
+    return fl;
+}
+
+// Wave totals of the per-lane sums of score_planes, packed two per reduction (per-lane
+// ranges: points [-192, 320], score [-64, 64], possible and side effects [0, 64], so
+// each total fits 16 bits).  A caller without side effects (wave_reset) passes 0.
+struct ScoreTotals {
+    int points, score, possible, side;
+};
+__device__ __forceinline__ ScoreTotals score_totals(int pts, int scr, int pos, int side) {
+    const int s1 = wave_total((pts + 192) | ((scr + 64) << 16));
+    const int s2 = wave_total(pos | (side << 16));
+    return ScoreTotals{(s1 & 0xFFFF) - 192 * 64, ((s1 >> 16) & 0xFFFF) - 64 * 64, s2 & 0xFFFF,
+                       (s2 >> 16) & 0xFFFF};
+}
+
+// exits (plane 8) in the colour the epilogue gives them (update_exit_colors): plane
+// 9 set when the env can exit, else clear.  Returns the cells whose plane 9 changed.
+struct Words2 {
+    u32 w[2];
+};
+__device__ __forceinline__ Words2 recolour_exits(u32 P[32], bool can) {
+    Words2 d9;
+#pragma unroll
+    for (int w = 0; w < 2; w++) {
+        const u32 o9 = PL(P, 9, w);
+        PL(P, 9, w) = can ? (o9 | PL(P, 8, w)) : (o9 & ~PL(P, 8, w));
+        d9.w[w] = o9 ^ PL(P, 9, w);
+    }
+    return d9;
+}
+
+// queue env b for the reset kernel that follows the step (one lane calls this)
+__device__ __forceinline__ void queue_reset(int64_t *scratch, int64_t B, uint32_t step, int64_t b) {
+    int64_t *cnt = scratch + 8 * B + 2 + (step & 1);
+    const int i = (int)atomicAdd((unsigned long long *)cnt, 1ull);
+    reset_list(scratch)[i] = (int32_t)b;
+}
 
 }  // namespace bits
 }  // namespace sl

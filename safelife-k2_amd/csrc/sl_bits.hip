@@ -254,13 +254,12 @@ __device__ __forceinline__ void wave_reset(const sl_env_state &st, const sl_leve
     transpose32(P);
     int pts, scr, pos, side;
     score_planes(P, gcol, P, &pts, &scr, &pos, &side);
-    const int s1 = wave_total((pts + 192) | ((scr + 64) << 16));
-    const int s2 = wave_total(pos);
+    const ScoreTotals t = score_totals(pts, scr, pos, 0);     // (no side effects yet)
     const bool sb = __ballot((PL(P, 7, 0) | PL(P, 7, 1)) != 0u) != 0ull;
     int ev = 0;
     if (lane == 0)
-        ev = reset_scalars_from(st, ra, b, li, dy, dx, ls, ep, (s1 & 0xFFFF) - 192 * 64,
-                                ((s1 >> 16) & 0xFFFF) - 64 * 64, s2, (sb ? 1 : 0) | (sg ? 2 : 0));
+        ev = reset_scalars_from(st, ra, b, li, dy, dx, ls, ep, t.points, t.score, t.possible,
+                                (sb ? 1 : 0) | (sg ? 2 : 0));
     ev = __builtin_amdgcn_readfirstlane(ev);
     const u32 ex0 = PL(P, 8, 0), ex1 = PL(P, 8, 1);       // exit planes
     // the board: the start board with its exits coloured (update_exit_colors)
@@ -543,6 +542,53 @@ __device__ __forceinline__ void issue_pre(const sl_env_state &st, const int32_t 
     }
 }
 
+// The goals' step of the two 64x64 kernels, for goals not at their fixed point (the
+// callers skip those: (pok & 6) == 6).  The goals come from their bit-plane mirror mg
+// when it is valid (pok bit 1; mg may be null: no mirror), else from the cells gg,
+// transposed; after the rule the mirror takes the words whose 32 cells changed (all of
+// them if rebuilt), gcol the new colour planes and gg the changed rows.  Returns the
+// goals' planes_ok bits after the step (pok without a mirror); the caller stores them.
+// PIN: rule_planes'.
+template <bool PIN, int MODE>
+__device__ __forceinline__ int goals_step64(u32 *gg, u32 *mg, int pok, int lane,
+                                            const SpawnCtx &sc, const StreamSrc &ssrc,
+                                            int64_t pos_g, u32 gcol[3][2]) {
+    int ok = pok;
+    u32 PG[32];
+    if (pok & 2) {
+#pragma unroll
+        for (int q = 0; q < 32; q++) PG[q] = mg[q * 64];    // goal planes
+    } else {
+        load_pairs_nt<32>(gg, PG);                              // goal cells
+        transpose32(PG);
+    }
+    u32 cg[2];
+    rule_planes<PIN>(PG, cg, Geo64<MODE>{lane, ssrc, pos_g, 0}, sc, 1u);
+    const u32 rg = wave_or(cg[0] | cg[1]);
+    if (mg) {
+        const bool all = !(pok & 2);
+#pragma unroll
+        for (int w = 0; w < 2; w++)
+            if (all || cg[w])
+#pragma unroll
+                for (int k = 0; k < 16; k++) mg[(k + 16 * w) * 64] = PL(PG, k, w);
+        const bool fixed = rg == 0 && __ballot((PL(PG, 7, 0) | PL(PG, 7, 1)) != 0u) == 0ull;
+        ok = 2 | (fixed ? 4 : 0);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        gcol[k][0] = PL(PG, 9 + k, 0);
+        gcol[k][1] = PL(PG, 9 + k, 1);
+    }
+    if (rg) {
+        transpose32(PG);
+#pragma unroll
+        for (int y = 0; y < 32; y++)
+            if ((rg >> y) & 1u) __builtin_nontemporal_store(PG[y], &gg[y * 32]);
+    }
+    return ok;
+}
+
 // One env-step of env b.  `pre` holds b's record and goal colour planes and b's board
 // is in flight into `buf` (issued by the caller).  MODE: SPAWN_PHILOX, or SPAWN_STREAM
 // (replay: k_env_action has run the action and k_stream_prologue64 sized the draws; the step reads
@@ -578,55 +624,14 @@ __device__ __forceinline__ void step_env(const sl_env_state &st, const StepArgs 
     }
     const int pok = (mg && st.planes_ok) ? rec(V, R_POK) & 6 : 0;
 
-    SpawnCtx sc;
-    sc.gid = a.env0 + (uint32_t)b;
-    sc.step = a.step;
-    sc.seed = a.seed;
-    set_spawn_prob(sc, __int_as_float(rec(V, R_SPAWN)));
-    StreamSrc ssrc{a.draws, a.n_draws, nullptr, a.draw_mask, a.draw_bits};
-    int64_t pos_b = 0, pos_g = 0;
-    if (MODE == SPAWN_STREAM) {
-        const Scratch w = scratch_of(fx.scratch, st.B);
-        ssrc.err = w.err;
-        pos_b = w.offsets[2 * b];
-        pos_g = w.offsets[2 * b + 1];
-    }
+    const SpawnCtx sc = spawn_ctx(a, b, rec(V, R_SPAWN));
+    int64_t pos_b, pos_g;
+    const StreamSrc ssrc = stream_src<MODE>(a, fx.scratch, st.B, b, pos_b, pos_g);
 
     // ---- goals
     if ((pok & 6) != 6) {
-        u32 PG[32];
-        if (pok & 2) {
-#pragma unroll
-            for (int q = 0; q < 32; q++) PG[q] = mg[q * 64];    // goal planes
-        } else {
-            load_pairs_nt<32>(gg, PG);                              // goal cells
-            transpose32(PG);
-        }
-        u32 cg[2];
-        rule_planes(PG, cg, Geo64<MODE>{lane, ssrc, pos_g, 0}, sc, 1u);
-        const u32 rg = wave_or(cg[0] | cg[1]);
-        if (mg) {      // mirror: the words whose 32 cells changed (all of them if rebuilt)
-            const bool all = !(pok & 2);
-#pragma unroll
-            for (int w = 0; w < 2; w++)
-                if (all || cg[w])
-#pragma unroll
-                    for (int k = 0; k < 16; k++) mg[(k + 16 * w) * 64] = PL(PG, k, w);
-            const bool fixed = rg == 0 && __ballot((PL(PG, 7, 0) | PL(PG, 7, 1)) != 0u) == 0ull;
-            const int ok = 2 | (fixed ? 4 : 0);
-            if (ok != pok && lane == 0) st.planes_ok[b] = ok;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            gcol[k][0] = PL(PG, 9 + k, 0);
-            gcol[k][1] = PL(PG, 9 + k, 1);
-        }
-        if (rg) {
-            transpose32(PG);
-#pragma unroll
-            for (int y = 0; y < 32; y++)
-                if ((rg >> y) & 1u) __builtin_nontemporal_store(PG[y], &gg[y * 32]);
-        }
+        const int ok = goals_step64<false, MODE>(gg, mg, pok, lane, sc, ssrc, pos_g, gcol);
+        if (ok != pok && lane == 0) st.planes_ok[b] = ok;
     }
     __builtin_amdgcn_sched_barrier(0);
 
@@ -636,7 +641,12 @@ __device__ __forceinline__ void step_env(const sl_env_state &st, const StepArgs 
     if (fx.pool.K > 0 && fx.pool.board_planes && st.start_roll) roll = rec(V, R_ROLL);
     wait_vm();
 
-    // the action (lane 0), on the staged board and the record
+    // the action (lane 0), on the staged board and the record.  (Kept copy: this
+    // prologue is written out here, in the plane kernel and in k_env_step_small.  A
+    // force-inlined sl_bits.h helper templated on the cell source -- building the
+    // overlay and RecEnv, returning RecFields, edits through out-parameters; or taking
+    // a caller-built RecEnv and returning only the reward -- left k_env_step_bits64<0,
+    // SPAWN_PHILOX> with 64 spilled VGPRs and 132 B of scratch.)
     OverlayT<LdsCells> ov;
     ov.src.buf = buf;
     ov.n = 0;
@@ -662,12 +672,9 @@ __device__ __forceinline__ void step_env(const sl_env_state &st, const StepArgs 
         eidx[k] = __builtin_amdgcn_readfirstlane(ov.idx[k]);
         eval[k] = (u32)__builtin_amdgcn_readfirstlane((int)ov.val[k]);
     }
-    RecFields fl{V, __builtin_amdgcn_readfirstlane(env.go), __builtin_amdgcn_readfirstlane(env.ax),
-                 __builtin_amdgcn_readfirstlane(env.ay), 0.0};
-    if (a.bonus_period > 0)        // issued now, consumed by the epilogue
-        fl.bval = a.bonus_table[bonus_dist(fl.ax, fl.ay, fl.prior_x(fl.prior_head()),
-                                           fl.prior_y(fl.prior_head()), fl.prior_len(),
-                                           a.bonus_period, a.bonus_len)];
+    const RecFields fl = rec_fields(a, V, __builtin_amdgcn_readfirstlane(env.go),
+                                    __builtin_amdgcn_readfirstlane(env.ax),
+                                    __builtin_amdgcn_readfirstlane(env.ay));
 
     u32 PB[32];
     read_pairs(buf, lane, PB);
@@ -707,25 +714,17 @@ __device__ __forceinline__ void step_env(const sl_env_state &st, const StepArgs 
     int pts, scr, pos, side;
     if (VIEW && !hi) score_planes<true>(PB, gcol, PS, &pts, &scr, &pos, &side);
     else score_planes(PB, gcol, PS, &pts, &scr, &pos, &side);
-    // totals (packed two per word: per-lane ranges [-192, 320] and [-64, 64]);
-    // reduced before the board store so the scoring is not sunk past it
-    const int s1 = wave_total((pts + 192) | ((scr + 64) << 16));
-    const int s2 = wave_total(pos | (side << 16));
+    // totals: reduced before the board store so the scoring is not sunk past it
+    const ScoreTotals tot = score_totals(pts, scr, pos, side);
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- write back the changed rows of the board, exits already in the colour the
     // epilogue gives them (update_exit_colors), so its exit writes and these row
     // stores carry the same values and need no ordering
-    const int points = (s1 & 0xFFFF) - 192 * 64;
-    const int score = ((s1 >> 16) & 0xFFFF) - 64 * 64;
-    const int possible = s2 & 0xFFFF;
-    const int side_total = (s2 >> 16) & 0xFFFF;
     const u32 rb = wave_or(cb[0] | cb[1]) | erow;
     if (rb || VIEW) {
-        const bool can = can_exit_now(fl.min_performance(), score, fl.baseline(), possible);
-#pragma unroll
-        for (int w = 0; w < 2; w++)
-            PL(PB, 9, w) = can ? (PL(PB, 9, w) | PL(PB, 8, w)) : (PL(PB, 9, w) & ~PL(PB, 8, w));
+        (void)recolour_exits(PB, can_exit_now(fl.min_performance(), tot.score, fl.baseline(),
+                                              tot.possible));
         transpose32(PB);
         if (VIEW && !hi) {
             lds_put_board(buf, lane, PB);      // the start board in buf has been read out
@@ -757,8 +756,8 @@ __device__ __forceinline__ void step_env(const sl_env_state &st, const StepArgs 
     }
     int reset = 0;
     if (lane == 0)
-        reset = epilogue_core(st, a, b, fl, act_reward, points, score, possible, side_total,
-                              reward_out, done_out, flags_out, ep_len_out, ep_rew_out);
+        reset = epilogue_core(st, a, b, fl, act_reward, tot.points, tot.score, tot.possible,
+                              tot.side, reward_out, done_out, flags_out, ep_len_out, ep_rew_out);
     reset = __builtin_amdgcn_readfirstlane(reset);
     if (VIEW && hi && !(fx.fuse_reset && reset)) {
         // a board using bits 12-14 (no cell type does): the view from the stored state
@@ -781,12 +780,8 @@ __device__ __forceinline__ void step_env(const sl_env_state &st, const StepArgs 
         else
             sl::obs::obs_packed_wave(st, oa, b, lane, lfx.obs_out);
     }
-    if (fx.fuse_reset && reset && lane == 0) {
-        // queue the env for the reset kernel (k_env_reset_list)
-        int64_t *cnt = fx.scratch + 8 * st.B + 2 + (a.step & 1);
-        const int i = (int)atomicAdd((unsigned long long *)cnt, 1ull);
-        reset_list(fx.scratch)[i] = (int32_t)b;
-    }
+    // queue the env for the reset kernel (k_env_reset_list)
+    if (fx.fuse_reset && reset && lane == 0) queue_reset(fx.scratch, st.B, a.step, b);
 }
 
 // OBS: also write the observation (fx.obs_out): 1 packed, 2-4 channel views
@@ -944,48 +939,15 @@ k_env_step_bits64_planes(StepKArgs ka) {
         gcol[k][1] = pre.g[k][1];
     }
     const int pok = pok_all & 6;
-    int gok = pok;                 // the goals' planes_ok bits after this step
 
-    SpawnCtx sc;
-    sc.gid = a.env0 + (uint32_t)b;
-    sc.step = a.step;
-    sc.seed = a.seed;
-    set_spawn_prob(sc, __int_as_float(rec(V, R_SPAWN)));
+    const SpawnCtx sc = spawn_ctx(a, b, rec(V, R_SPAWN));
     const StreamSrc ssrc{a.draws, a.n_draws, nullptr, a.draw_mask, a.draw_bits};
 
-    // ---- goals (as in step_env: the mirror in half 1, the fixed-point skip)
-    if ((pok & 6) != 6) {
-        u32 PG[32];
-        if (pok & 2) {
-#pragma unroll
-            for (int q = 0; q < 32; q++) PG[q] = mg[q * 64];
-        } else {
-            load_pairs_nt<32>(gg, PG);
-            transpose32(PG);
-        }
-        u32 cg[2];
-        rule_planes<true>(PG, cg, Geo64<SPAWN_PHILOX>{lane, ssrc, 0, 0}, sc, 1u);
-        const u32 rg = wave_or(cg[0] | cg[1]);
-        const bool all = !(pok & 2);
-#pragma unroll
-        for (int w = 0; w < 2; w++)
-            if (all || cg[w])
-#pragma unroll
-                for (int k = 0; k < 16; k++) mg[(k + 16 * w) * 64] = PL(PG, k, w);
-        const bool fixed = rg == 0 && __ballot((PL(PG, 7, 0) | PL(PG, 7, 1)) != 0u) == 0ull;
-        gok = 2 | (fixed ? 4 : 0);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            gcol[k][0] = PL(PG, 9 + k, 0);
-            gcol[k][1] = PL(PG, 9 + k, 1);
-        }
-        if (rg) {
-            transpose32(PG);
-#pragma unroll
-            for (int y = 0; y < 32; y++)
-                if ((rg >> y) & 1u) __builtin_nontemporal_store(PG[y], &gg[y * 32]);
-        }
-    }
+    // ---- goals: the mirror is half 1 of the planes; their planes_ok bits after this
+    // step go out with the board's below
+    int gok = pok;
+    if ((pok & 6) != 6)
+        gok = goals_step64<true, SPAWN_PHILOX>(gg, mg, pok, lane, sc, ssrc, 0, gcol);
     __builtin_amdgcn_sched_barrier(0);
 
     int roll = -1;
@@ -1006,6 +968,7 @@ k_env_step_bits64_planes(StepKArgs ka) {
         __builtin_amdgcn_wave_barrier();
     }
     // the action (lane 0) on the cells round the agent, gathered from the staged planes
+    // (kept copy of step_env's prologue: see there)
     RecEnv env{st, b, rec(V, R_GO), rec(V, R_AX), rec(V, R_AY), rec(V, R_SCORE),
                rec(V, R_BASE), rec(V, R_POSS), rec_f64(V, R_MP)};
     int act_reward = 0;
@@ -1038,12 +1001,9 @@ k_env_step_bits64_planes(StepKArgs ka) {
         // edited one included: said here, the planes not kept stay constants below
         if (K16) eval[k] &= K16;
     }
-    RecFields fl{V, __builtin_amdgcn_readfirstlane(env.go), __builtin_amdgcn_readfirstlane(env.ax),
-                 __builtin_amdgcn_readfirstlane(env.ay), 0.0};
-    if (a.bonus_period > 0)        // issued now, consumed by the epilogue
-        fl.bval = a.bonus_table[bonus_dist(fl.ax, fl.ay, fl.prior_x(fl.prior_head()),
-                                           fl.prior_y(fl.prior_head()), fl.prior_len(),
-                                           a.bonus_period, a.bonus_len)];
+    const RecFields fl = rec_fields(a, V, __builtin_amdgcn_readfirstlane(env.go),
+                                    __builtin_amdgcn_readfirstlane(env.ax),
+                                    __builtin_amdgcn_readfirstlane(env.ay));
 
     u32 PB[32];
 #pragma unroll
@@ -1081,24 +1041,13 @@ k_env_step_bits64_planes(StepKArgs ka) {
     }
     int pts, scr, pos, side;
     score_planes(PB, gcol, PS, &pts, &scr, &pos, &side);
-    const int s1 = wave_total((pts + 192) | ((scr + 64) << 16));
-    const int s2 = wave_total(pos | (side << 16));
+    const ScoreTotals tot = score_totals(pts, scr, pos, side);
     __builtin_amdgcn_sched_barrier(0);
-    const int points = (s1 & 0xFFFF) - 192 * 64;
-    const int score = ((s1 >> 16) & 0xFFFF) - 64 * 64;
-    const int possible = s2 & 0xFFFF;
-    const int side_total = (s2 >> 16) & 0xFFFF;
 
     // ---- exits in the colour the epilogue gives them (update_exit_colors), then the
     // plane words that changed (all of them on a step into plane mode)
-    const bool can = can_exit_now(fl.min_performance(), score, fl.baseline(), possible);
-    u32 d9[2];
-#pragma unroll
-    for (int w = 0; w < 2; w++) {
-        const u32 o9 = PL(PB, 9, w);
-        PL(PB, 9, w) = can ? (o9 | PL(PB, 8, w)) : (o9 & ~PL(PB, 8, w));
-        d9[w] = o9 ^ PL(PB, 9, w);
-    }
+    const Words2 d9 = recolour_exits(
+        PB, can_exit_now(fl.min_performance(), tot.score, fl.baseline(), tot.possible));
     u32 em[2] = {0u, 0u};           // the words the action's edits touched (this lane's)
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -1114,14 +1063,14 @@ k_env_step_bits64_planes(StepKArgs ka) {
         dw[w] = cb[w] | em[w];                       // words whose cells changed
         dall[w] = em[w] | (((held_lanes >> lane) & 1ull) ? cb[w] : 0u);   // ... other planes
     }
-    if (!pin || wave_or(dw[0] | dw[1] | d9[0] | d9[1])) {
+    if (!pin || wave_or(dw[0] | dw[1] | d9.w[0] | d9.w[1])) {
 #pragma unroll
         for (int k = 0; k < 16; k++) {
             if (!ps.kept(k)) continue;
 #pragma unroll
             for (int w = 0; w < 2; w++) {
                 const u32 d = (k == 0 || k == 3 || k == 10 || k == 11) ? dw[w]
-                              : k == 9 ? (dw[w] | d9[w]) : dall[w];
+                              : k == 9 ? (dw[w] | d9.w[w]) : dall[w];
                 if (!pin || d)
                     __builtin_nontemporal_store(PL(PB, k, w), &bp[ps.pos(k + 16 * w) * 64]);
             }
@@ -1161,15 +1110,11 @@ k_env_step_bits64_planes(StepKArgs ka) {
     }
     int reset = 0;
     if (lane == 0)
-        reset = epilogue_core(st, a, b, fl, act_reward, points, score, possible, side_total,
-                              ka.reward_out, ka.done_out, ka.flags_out, ka.ep_len_out,
+        reset = epilogue_core(st, a, b, fl, act_reward, tot.points, tot.score, tot.possible,
+                              tot.side, ka.reward_out, ka.done_out, ka.flags_out, ka.ep_len_out,
                               ka.ep_rew_out);
     reset = __builtin_amdgcn_readfirstlane(reset);
-    if (fx.fuse_reset && reset && lane == 0) {
-        int64_t *cnt = fx.scratch + 8 * st.B + 2 + (a.step & 1);
-        const int i = (int)atomicAdd((unsigned long long *)cnt, 1ull);
-        reset_list(fx.scratch)[i] = (int32_t)b;
-    }
+    if (fx.fuse_reset && reset && lane == 0) queue_reset(fx.scratch, st.B, a.step, b);
 }
 
 // sl_env_board_sync for 64x64 boards in planes: one wave per env

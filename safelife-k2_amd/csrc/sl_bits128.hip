@@ -475,18 +475,9 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
     const LanePtr<u32> me{MODE == SPAWN_DECIDED ? st.elig_planes + b * kEligStride : nullptr};
     const int dfl = MODE == SPAWN_DECIDED ? (int)w.act[st.B + b] : 0;
 
-    SpawnCtx sc;
-    sc.gid = a.env0 + (uint32_t)b;
-    sc.step = a.step;
-    sc.seed = a.seed;
-    set_spawn_prob(sc, __int_as_float(rec(V, R_SPAWN)));
-    StreamSrc ssrc{a.draws, a.n_draws, nullptr, a.draw_mask, a.draw_bits};
-    int64_t pos_b = 0, pos_g = 0;
-    if (MODE == SPAWN_STREAM) {
-        ssrc.err = w.err;
-        pos_b = w.offsets[2 * b];
-        pos_g = w.offsets[2 * b + 1];
-    }
+    const SpawnCtx sc = spawn_ctx(a, b, rec(V, R_SPAWN));
+    int64_t pos_b, pos_g;
+    const StreamSrc ssrc = stream_src<MODE>(a, fx.scratch, st.B, b, pos_b, pos_g);
     // Bands are processed in order 0..3, so the pre-step halo rows of band t are band
     // t - 1's last row (kept from its load: it is written back before band t runs),
     // and band t + 1's first row (not yet written); band 3's lower halo is row 0,
@@ -838,11 +829,7 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
     const ViewExit vex = VIEW ? view_exits_load(k.st, b, agy, agx) : ViewExit{-1, 0u};
     const u32 VE = load_record(k.st, k.actions, b, lane_now());
     const int act_reward = (int)scratch_of(k.fx.scratch, k.st.B).act[b];
-    RecFields fl{VE, rec(VE, R_GO), rec(VE, R_AX), rec(VE, R_AY), 0.0};
-    if (k.a.bonus_period > 0)
-        fl.bval = k.a.bonus_table[bonus_dist(fl.ax, fl.ay, fl.prior_x(fl.prior_head()),
-                                             fl.prior_y(fl.prior_head()), fl.prior_len(),
-                                             k.a.bonus_period, k.a.bonus_len)];
+    const RecFields fl = rec_fields(k.a, VE, rec(VE, R_GO), rec(VE, R_AX), rec(VE, R_AY));
     wait_vm();              // row stores land before the epilogue rewrites the exits
     int can = 0;
     if (lane_now() == 0) {
@@ -851,11 +838,8 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
         const bool reset = epilogue_core(k.st, k.a, b, fl, act_reward, points, score, possible,
                                          side_total, k.reward_out, k.done_out, k.flags_out,
                                          k.ep_len_out, k.ep_rew_out, &can);
-        if (k.fx.fuse_reset && reset) {   // queued for k_env_reset_list_wide
-            int64_t *cnt = k.fx.scratch + 8 * k.st.B + 2 + (k.a.step & 1);
-            const int i = (int)atomicAdd((unsigned long long *)cnt, 1ull);
-            reset_list(k.fx.scratch)[i] = (int32_t)b;
-        }
+        // queued for k_env_reset_list_wide
+        if (k.fx.fuse_reset && reset) queue_reset(k.fx.scratch, k.st.B, k.a.step, b);
     }
     // (the view's band stores have completed: wait_vm above)
     if (VIEW) view_exits_store(vex, b, __builtin_amdgcn_readfirstlane(can));
@@ -1130,7 +1114,7 @@ k_stream_prologue128(Step128KArgs ka) {
 // the partner word (lane ^ s) from ds_swizzle, the swapped block by a rotation and a
 // bitfield insert.
 template <int S, u32 M>
-__device__ __forceinline__ u32 swap_stage(u32 x, int lane) {
+__device__ __forceinline__ u32 lane_swap_stage(u32 x, int lane) {
     const bool hi = (lane & S) != 0;
     const u32 p = (u32)__builtin_amdgcn_ds_swizzle((int)x, 0x1F | (S << 10));
     const u32 sh = __builtin_amdgcn_alignbit(p, p, hi ? S : 32 - S);     // rotate
@@ -1138,11 +1122,11 @@ __device__ __forceinline__ u32 swap_stage(u32 x, int lane) {
     return (x & mm) | (sh & ~mm);
 }
 __device__ __forceinline__ u32 transpose_halves(u32 x, int lane) {
-    x = swap_stage<16, 0x0000FFFFu>(x, lane);
-    x = swap_stage<8, 0x00FF00FFu>(x, lane);
-    x = swap_stage<4, 0x0F0F0F0Fu>(x, lane);
-    x = swap_stage<2, 0x33333333u>(x, lane);
-    return swap_stage<1, 0x55555555u>(x, lane);
+    x = lane_swap_stage<16, 0x0000FFFFu>(x, lane);
+    x = lane_swap_stage<8, 0x00FF00FFu>(x, lane);
+    x = lane_swap_stage<4, 0x0F0F0F0Fu>(x, lane);
+    x = lane_swap_stage<2, 0x33333333u>(x, lane);
+    return lane_swap_stage<1, 0x55555555u>(x, lane);
 }
 
 // inclusive sum over the lanes of each 32-lane half

@@ -288,13 +288,8 @@ k_env_step_small(SmallKArgs ka) {
     const bool active = lane < nl;
     const int c0 = 2 * lane, c1 = 2 * lane + 1;             // stores: c1 < W unless odd_last
     GeoSmall<MODE> geo = small_geo<MODE>(lane, H, W);
-    int64_t pos_b = 0, pos_g = 0;
-    if (MODE == SPAWN_STREAM) {
-        const Scratch w = scratch_of(ka.scratch, st.B);
-        geo.src = StreamSrc{a.draws, a.n_draws, w.err, a.draw_mask, a.draw_bits};
-        pos_b = w.offsets[2 * b];
-        pos_g = w.offsets[2 * b + 1];
-    }
+    int64_t pos_b, pos_g;
+    geo.src = stream_src<MODE>(a, ka.scratch, st.B, b, pos_b, pos_g);
     // valid cells per word: rows < H of real columns
     const u32 wm0 = active ? geo.mh : 0u, wm1 = (active && !geo.odd_last) ? geo.mh : 0u;
 
@@ -310,11 +305,7 @@ k_env_step_small(SmallKArgs ka) {
     u32 PB[32], PG[32];
     lds_rows((const lds_u16 *)stage[1], H, active, lane, PG);
 
-    SpawnCtx sc;
-    sc.gid = a.env0 + (uint32_t)b;
-    sc.step = a.step;
-    sc.seed = a.seed;
-    set_spawn_prob(sc, __int_as_float(rec(V, R_SPAWN)));
+    const SpawnCtx sc = spawn_ctx(a, b, rec(V, R_SPAWN));
 
     // ---- goals: rule, then store the changed rows
     transpose32(PG);
@@ -343,6 +334,7 @@ k_env_step_small(SmallKArgs ka) {
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- board: the action reads the staged cells, then the rows become planes
+    // (kept copy of the 64x64 kernels' action prologue: see step_env, sl_bits.hip)
     OverlayT<SmallCells> ov;
     ov.src.buf = buf;
     ov.n = 0;
@@ -376,12 +368,9 @@ k_env_step_small(SmallKArgs ka) {
             }
     }
     erow = (u32)__builtin_amdgcn_readfirstlane((int)erow);
-    RecFields fl{V, __builtin_amdgcn_readfirstlane(env.go), __builtin_amdgcn_readfirstlane(env.ax),
-                 __builtin_amdgcn_readfirstlane(env.ay), 0.0};
-    if (a.bonus_period > 0)
-        fl.bval = a.bonus_table[bonus_dist(fl.ax, fl.ay, fl.prior_x(fl.prior_head()),
-                                           fl.prior_y(fl.prior_head()), fl.prior_len(),
-                                           a.bonus_period, a.bonus_len)];
+    const RecFields fl = rec_fields(a, V, __builtin_amdgcn_readfirstlane(env.go),
+                                    __builtin_amdgcn_readfirstlane(env.ax),
+                                    __builtin_amdgcn_readfirstlane(env.ay));
     lds_rows((const lds_u16 *)stage[0], H, active, lane, PB);
     transpose32(PB);
     u32 cb[2];
@@ -402,21 +391,14 @@ k_env_step_small(SmallKArgs ka) {
     }
     int pts, scr, pos, side;
     score_planes(PB, gcol, PS, &pts, &scr, &pos, &side);
-    const int s1 = wave_total((pts + 192) | ((scr + 64) << 16));
-    const int s2 = wave_total(pos | (side << 16));
-    const int points = (s1 & 0xFFFF) - 192 * 64;
-    const int score = ((s1 >> 16) & 0xFFFF) - 64 * 64;
-    const int possible = s2 & 0xFFFF;
-    const int side_total = (s2 >> 16) & 0xFFFF;
+    const ScoreTotals tot = score_totals(pts, scr, pos, side);
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- changed rows, exits in the colour the epilogue gives them
     const u32 rb = wave_or((cb[0] & wm0) | (cb[1] & wm1)) | erow;
     if (rb) {
-        const bool can = can_exit_now(fl.min_performance(), score, fl.baseline(), possible);
-#pragma unroll
-        for (int w = 0; w < 2; w++)
-            PL(PB, 9, w) = can ? (PL(PB, 9, w) | PL(PB, 8, w)) : (PL(PB, 9, w) & ~PL(PB, 8, w));
+        (void)recolour_exits(PB, can_exit_now(fl.min_performance(), tot.score, fl.baseline(),
+                                              tot.possible));
         transpose32(PB);
         uint16_t *gb = st.board + off;
 #pragma unroll
@@ -429,8 +411,9 @@ k_env_step_small(SmallKArgs ka) {
     int rs = 0;
     if (lane == 0) {
         const SmallKArgs &k = kargs();
-        rs = epilogue_core(k.st, k.a, b, fl, act_reward, points, score, possible, side_total,
-                           k.reward_out, k.done_out, k.flags_out, k.ep_len_out, k.ep_rew_out)
+        rs = epilogue_core(k.st, k.a, b, fl, act_reward, tot.points, tot.score, tot.possible,
+                           tot.side, k.reward_out, k.done_out, k.flags_out, k.ep_len_out,
+                           k.ep_rew_out)
                  ? 1 : 0;
     }
     rs = __builtin_amdgcn_readfirstlane(rs);
@@ -741,11 +724,7 @@ k_env_step_seg4(SmallKArgs ka) {
     u32 PB[32], PG[32];
     seg_rows(sg, H, W, holds, js, geo.odd_last, PG);
 
-    SpawnCtx sc;
-    sc.gid = a.env0 + (uint32_t)b;
-    sc.step = a.step;
-    sc.seed = a.seed;
-    set_spawn_prob(sc, __int_as_float(rc.get(R_SPAWN)));
+    const SpawnCtx sc = spawn_ctx(a, b, rc.get(R_SPAWN));
 
     // ---- goals: rule, then store the changed rows
     transpose32(PG);
@@ -863,12 +842,10 @@ k_env_step_seg4(SmallKArgs ka) {
     // changed -- by the rule, the action or an exit's colour -- are stored
     const bool can = can_exit_now(fl.mp, score, fl.base, possible);
     u32 ch = (cb[0] & wm0) | (cb[1] & wm1);
+    (void)recolour_exits(PB, can);
 #pragma unroll
-    for (int w = 0; w < 2; w++) {
-        const u32 n9 = can ? (PL(PB, 9, w) | PL(PB, 8, w)) : (PL(PB, 9, w) & ~PL(PB, 8, w));
-        ch |= (n9 ^ (PL(PB, 8, w) & (w ? old9[1] : old9[0]))) & PL(PB, 8, w) & (w ? wm1 : wm0);
-        PL(PB, 9, w) = n9;
-    }
+    for (int w = 0; w < 2; w++)      // against the colour the exits were loaded with
+        ch |= (PL(PB, 9, w) ^ (PL(PB, 8, w) & old9[w])) & PL(PB, 8, w) & (w ? wm1 : wm0);
     const u32 rb = seg_or(ch) | erow;
     if (__ballot(rb != 0u)) {
         transpose32(PB);

@@ -1,4 +1,4 @@
-"""Register and LDS budget of the 64x64 plane kernel, from the compiler's own remarks.
+"""Register and LDS budgets of the step kernels, from the compiler's own remarks.
 
 k_env_step_bits64_planes (sl_bits.hip) stages its board by LDS DMA, so no instantiation
 may spill, and the headline one -- the C3 / C4 planes (0x877F = 34687)
@@ -12,6 +12,7 @@ import os
 import re
 import shutil
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
@@ -31,25 +32,38 @@ def _makefile_flags():
     return flags.replace("$(ARCH)", arch).split()
 
 
+STEP_FILES = ("sl_bits", "sl_bits_small", "sl_bits128")
+
+
+def _remarks(out, name):
+    """(return code, stderr) of compiling csrc/<name>.hip, device only, with the remarks."""
+    p = subprocess.run([HIPCC] + _makefile_flags() +
+                       ["--cuda-device-only", "-S", os.path.join(CSRC, name + ".hip"),
+                        "-o", str(out / (name + ".s")), "-Rpass-analysis=kernel-resource-usage"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    return p.returncode, p.stderr
+
+
 @pytest.fixture(scope="module")
 def resources(tmp_path_factory):
-    """{mangled kernel name: {remark field: int}} of sl_bits.hip's kernels."""
+    """{mangled kernel name: {remark field: int}} of the step files' kernels (the three
+    files compiled concurrently, one compiler process each)."""
     out = tmp_path_factory.mktemp("res")
-    p = subprocess.run([HIPCC] + _makefile_flags() +
-                       ["--cuda-device-only", "-S", os.path.join(CSRC, "sl_bits.hip"),
-                        "-o", str(out / "sl_bits.s"), "-Rpass-analysis=kernel-resource-usage"],
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    res, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"remark:\s+(.*?):\s+(\S+)\s+\[-Rpass-analysis", line)
-        if not m:
-            continue
-        key, val = m.group(1).strip(), m.group(2)
-        if key == "Function Name":
-            cur = res.setdefault(val, {})
-        elif cur is not None and val.lstrip("-").isdigit():
-            cur[key] = int(val)
+    with ThreadPoolExecutor(max_workers=len(STEP_FILES)) as pool:
+        runs = list(pool.map(lambda name: _remarks(out, name), STEP_FILES))
+    res = {}
+    for rc, err in runs:
+        assert rc == 0, err[-2000:]
+        cur = None
+        for line in err.splitlines():
+            m = re.search(r"remark:\s+(.*?):\s+(\S+)\s+\[-Rpass-analysis", line)
+            if not m:
+                continue
+            key, val = m.group(1).strip(), m.group(2)
+            if key == "Function Name":
+                cur = res.setdefault(val, {})
+            elif cur is not None and val.lstrip("-").isdigit():
+                cur[key] = int(val)
     return res
 
 
@@ -72,3 +86,43 @@ def test_headline_plane_kernel_fits_five_waves(resources):
     assert r["Occupancy [waves/SIMD]"] == 5, r
     assert r["VGPRs"] <= 96, r
     assert r["LDS Size [bytes/block]"] <= 8192, r
+
+
+# Waves per SIMD of every k_env_step_* instance, by the template arguments' mangling.
+# Taken from compiling the commit BEFORE the step phases were shared in sl_bits.h (not
+# from the code under test): sharing code must not cost any instance a wave.
+PARENT_OCCUPANCY = {
+    "k_env_step_bits64I": {"Li0ELi0E": 4, "Li1ELi0E": 4, "Li2ELi0E": 4, "Li3ELi0E": 4,
+                           "Li4ELi0E": 4, "Li0ELi1E": 3, "Li1ELi1E": 3, "Li2ELi1E": 3,
+                           "Li3ELi1E": 3, "Li4ELi1E": 3},
+    "k_env_step_bits64_planesI": {"Lj34687ELi0E": 5, "Lj65535ELi0E": 4, "Lj0ELi0E": 4,
+                                  "Lj34687ELi1E": 4, "Lj65535ELi1E": 4, "Lj0ELi1E": 4},
+    "k_env_step_smallI": {"Li0E": 3, "Li1E": 3},
+    "k_env_step_seg4I": {"Li0ELb0E": 2, "Li0ELb1E": 2, "Li1ELb0E": 2, "Li1ELb1E": 2},
+    "k_env_step_bits128I": {"Li0ELj2043E": 4, "Li0ELj65535E": 4, "Li1ELj65535E": 3,
+                            "Li3ELj2043E": 4, "Li3ELj65535E": 4},
+    "k_env_step_bits128_viewI": {"Li0ELj2043E": 4, "Li0ELj65535E": 4, "Li3ELj2043E": 4,
+                                 "Li3ELj65535E": 4},
+}
+
+
+def test_step_kernels_keep_their_waves_and_do_not_spill(resources):
+    """Every k_env_step_* instance: occupancy not below the parent commit's, no VGPR
+    spill, no scratch.  PARENT_OCCUPANCY holds the parent's values (compiled from the
+    commit before this test was widened), so a change that costs a wave fails here;
+    the instance counts (10 + 6 in sl_bits, 2 + 4 in sl_bits_small, 5 + 4 = 9 in
+    sl_bits128) catch a dropped instantiation."""
+    step = {k: v for k, v in resources.items() if "k_env_step_" in k}
+    seen = 0
+    for family, table in PARENT_OCCUPANCY.items():
+        inst = {k: v for k, v in step.items() if family in k}
+        assert len(inst) == len(table), (family, sorted(inst))
+        for args, occ in table.items():
+            hit = [(k, v) for k, v in inst.items() if family + args + "E" in k]
+            assert len(hit) == 1, (family, args, sorted(inst))
+            name, r = hit[0]
+            assert r["Occupancy [waves/SIMD]"] >= occ, (name, r)
+            assert r["VGPRs Spill"] == 0, (name, r)
+            assert r["ScratchSize [bytes/lane]"] == 0, (name, r)
+            seen += 1
+    assert seen == len(step) == 10 + 6 + 2 + 4 + 9, sorted(step)
