@@ -391,8 +391,11 @@ typedef struct sl_env_state {
                                  board clears planes_ok (as for the goals
                                  mirror).  64x64: board_planes == planes puts
                                  the board's planes in half 0 of the goals
-                                 mirror (Philox steps without views; bit 7
-                                 only after a sync or a reset).                */
+                                 mirror (Philox steps without capture: with no
+                                 obs_out, with packed views, or with channel
+                                 views of at most 64x64 and 1094 cells into a
+                                 16-byte aligned obs_out, all written from the
+                                 planes; bit 7 only after a sync).             */
     uint32_t board_zero;      /* plane mode (64x64, 128x128): cell bits (planes) that are
                                  0 in every board of the batch and that no rule,
                                  action or reset can set (the caller's promise:
@@ -498,8 +501,11 @@ typedef struct sl_env_cfg {
                                        observation after the step (auto-resets
                                        included), exactly as sl_env_obs with the
                                        fields below would; NULL = no observation.
-                                       The 64x64 kernel writes packed views from
-                                       the board it holds on chip (no re-read) */
+                                       The 64x64 kernels write packed views, and
+                                       channel views of at most 64x64 and 1094
+                                       cells into a 16-byte aligned obs_out, from
+                                       the board they hold on chip (no re-read;
+                                       in plane mode from the planes, which stay) */
     int32_t obs_mode, obs_vh, obs_vw, obs_remove_white, obs_nch;
     int32_t obs_channels[16];
     const sl_capture *capture;      /* host pointer or NULL: trajectory capture

@@ -954,7 +954,8 @@ extern "C" int sl_env_reset(sl_env_state *st, const sl_level_pool *pool, const u
 
 // The board planes' sync (sync_board_planes), skipped while no step of this state has
 // left a board in planes since the last demotion (sl_env_state.planes_live: a step that
-// is not in plane mode, e.g. with channel views, launched no-op syncs otherwise)
+// is not in plane mode, e.g. with views the step kernel cannot write, launched no-op
+// syncs otherwise)
 static int sync_planes(const sl_env_state *st, hipStream_t s) {
     return st->planes_live ? sync_board_planes(*st, 0, s) : SL_OK;
 }
@@ -1059,18 +1060,6 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
                              oa.vh <= kViewMaxRows128 && oa.vw <= 128;
     fx.plane_mode = (fast128 && planes128 && (!cfg->obs_out || fuse_obs128) && !cap &&
                      (!replay || st->elig_planes) && cfg->board_mode != SL_BOARD_UINT16) ? 1 : 0;
-    // 64x64: a Philox step without views or capture (sl_bits.hip, plane mode)
-    const bool planes64 = planes64_shape(*st);
-    if (planes64)       // (packed views: written from the planes, fused_obs64 below)
-        fx.plane_mode = (fast && !cap && !replay && cfg->board_mode != SL_BOARD_UINT16 &&
-                         (!cfg->obs_out || (oa.mode == SL_OBS_PACKED &&
-                                            oa.vh * oa.vw <= kObsMaxCells))) ? 1 : 0;
-    if ((planes128 || planes64) && !fx.plane_mode) {
-        const int rc = demote_planes(st, s);
-        if (rc) return rc;
-    }
-    // (a plane-mode step below leaves boards in planes)
-    if (fx.plane_mode && cfg->stream_phase != 1) st->planes_live = 1;
     // observations: packed views of 64x64 boards come out of the step kernel itself
     // ... and channel views too (one wave writes its env's 16-byte chunks from the
     // view masks it builds in LDS: views up to kFusedChanCells cells, 16-B aligned out)
@@ -1079,6 +1068,18 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
         ((oa.mode == SL_OBS_PACKED && oa.vh * oa.vw <= kObsMaxCells) ||
          (oa.mode != SL_OBS_PACKED && oa.vh <= 64 && oa.vw <= 64 &&
           oa.vh * oa.vw + 2 <= kFusedChanCells && (((uintptr_t)cfg->obs_out) & 15) == 0));
+    // 64x64: a Philox step without capture and with no views, or with views the step
+    // kernel writes itself (fuse_obs: from the planes, sl_bits.hip, plane mode)
+    const bool planes64 = planes64_shape(*st);
+    if (planes64)
+        fx.plane_mode = (fast && !cap && !replay && cfg->board_mode != SL_BOARD_UINT16 &&
+                         (!cfg->obs_out || fuse_obs)) ? 1 : 0;
+    if ((planes128 || planes64) && !fx.plane_mode) {
+        const int rc = demote_planes(st, s);
+        if (rc) return rc;
+    }
+    // (a plane-mode step below leaves boards in planes)
+    if (fx.plane_mode && cfg->stream_phase != 1) st->planes_live = 1;
     fx.obs_out = (fuse_obs || fuse_obs128) ? (uint16_t *)cfg->obs_out : nullptr;
     fx.obs_vh = cfg->obs_vh;
     fx.obs_vw = cfg->obs_vw;

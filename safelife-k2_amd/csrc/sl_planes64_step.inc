@@ -1,0 +1,217 @@
+// sl_planes64_step.inc -- one plane-mode env-step of env blockIdx.x: the body of the
+// kernels k_env_step_bits64_planes and k_env_planes64_chan (sl_bits.hip), included inside
+// each.  (Text, not a force-inlined function: as a function templated on <K16, OBS> and
+// called from thin kernels, the same statements left k_env_step_bits64_planes<0x877F, 0>
+// with 3692 spilled VGPRs and 3112 B of scratch at its 96-register budget, and moved the
+// run-time-mask instances by two registers; included, the six older kernels compile to
+// the instructions they had.)  In scope where it is included: the template parameters K16
+// (kept planes; 0: from board_zero) and OBS (k_env_step_bits64's: 0 none, 1 packed views
+// by write_obs, 2-4 channel views by write_obs_channels<obs_esz(OBS)>), the kernel's
+// argument `StepKArgs ka`, the wave's buffer `u32 stage[N * N / 2]` in LDS, and `vm`, the
+// view's channel masks in LDS (uint16_t[kFusedChanCells]; unused when OBS < 2).
+// With views, the goal colours are added into planes 12-14 (a bit-sliced adder, exact
+// whatever the board's bits), ONE transpose puts the view-form rows into the buffer.
+    const sl_env_state &st = ka.st;
+    const StepArgs &a = ka.a;
+    const FastExtra &fx = ka.fx;
+    const int64_t b = blockIdx.x;          // one wave per env
+    const int lane = threadIdx.x;
+    lds_u32 *buf = (lds_u32 *)&stage[0];
+    const PlaneSlots<K16> ps = PlaneSlots<K16>::of(st.board_zero);
+    Pre pre;
+    issue_pre(st, ka.actions, b, lane, pre);
+    // the board's planes, speculatively: an env whose planes do not hold its board (the
+    // first step after a host write or a step in another mode) reloads its rows below
+    dma_planes(st.planes + b * 4096, ps, buf, lane);
+    const int64_t off = b * (int64_t)(N * N);
+    const int lane_off = (lane & 1) * 1024 + (lane >> 1);     // dwords: row 32h, column pair j
+    u32 *gg = reinterpret_cast<u32 *>(st.goals + off) + lane_off;
+    u32 *mg = st.planes + b * 4096 + 2048 + lane;
+    u32 *bp = st.planes + b * 4096 + lane;
+    const u32 V = pre.V;
+    const int pok_all = rec(V, R_POK);
+    const bool pin = (pok_all & kPok64Board) != 0;
+    u32 gcol[3][2];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        gcol[k][0] = pre.g[k][0];
+        gcol[k][1] = pre.g[k][1];
+    }
+    const int pok = pok_all & 6;
+
+    const SpawnCtx sc = spawn_ctx(a, b, rec(V, R_SPAWN));
+    const StreamSrc ssrc{a.draws, a.n_draws, nullptr, a.draw_mask, a.draw_bits};
+
+    // ---- goals: the mirror is half 1 of the planes; their planes_ok bits after this
+    // step go out with the board's below
+    int gok = pok;
+    if ((pok & 6) != 6)
+        gok = goals_step64<true, SPAWN_PHILOX>(gg, mg, pok, lane, sc, ssrc, 0, gcol);
+    __builtin_amdgcn_sched_barrier(0);
+
+    int roll = -1;
+    if (fx.pool.K > 0 && fx.pool.board_planes && st.start_roll) roll = rec(V, R_ROLL);
+    wait_vm();
+    if (!pin) {
+        // a step into plane mode: the uint16 board instead, transposed and put into the
+        // buffer in the planes' layout, so everything below reads planes
+        dma_board(st.board + off, buf, lane);
+        wait_vm();
+        u32 R[32];
+        read_pairs(buf, lane, R);
+        transpose32(R);
+#pragma unroll
+        for (int q = 0; q < 32; q++)
+            if (ps.kept(q)) buf[ps.pos(q) * 64 + lane] = R[q];
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    // the action (lane 0) on the cells round the agent, gathered from the staged planes
+    // (kept copy of step_env's prologue: see there)
+    RecEnv env{st, b, rec(V, R_GO), rec(V, R_AX), rec(V, R_AY), rec(V, R_SCORE),
+               rec(V, R_BASE), rec(V, R_POSS), rec_f64(V, R_MP)};
+    int act_reward = 0;
+    int eidx[4];
+    u32 eval[4];
+    const int ay0 = rec(V, R_AY), ax0 = rec(V, R_AX);
+    const u32 near = lane < 9 ? lds_plane_cell(buf, ps, near_cell_index(lane, ay0, ax0)) : 0u;
+    OverlayT<NearCells> ov;
+    ov.src = NearCells{ay0, ax0, near};
+    ov.n = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        ov.idx[k] = 0;
+        ov.val[k] = 0;
+    }
+    if (lane == 0) act_reward = act_core(env, rec(V, R_ACT), N, N, ka.ctp, ka.ctc, ov);
+    int ne = ov.n;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        eidx[k] = ov.idx[k];
+        eval[k] = ov.val[k];
+    }
+    act_reward = __builtin_amdgcn_readfirstlane(act_reward);
+    ne = __builtin_amdgcn_readfirstlane(ne);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        eidx[k] = __builtin_amdgcn_readfirstlane(eidx[k]);
+        eval[k] = (u32)__builtin_amdgcn_readfirstlane((int)eval[k]);
+        // no cell of the batch holds a bit outside the kept planes (board_zero), an
+        // edited one included: said here, the planes not kept stay constants below
+        if (K16) eval[k] &= K16;
+    }
+    const RecFields fl = rec_fields(a, V, __builtin_amdgcn_readfirstlane(env.go),
+                                    __builtin_amdgcn_readfirstlane(env.ax),
+                                    __builtin_amdgcn_readfirstlane(env.ay));
+
+    u32 PB[32];
+#pragma unroll
+    for (int q = 0; q < 32; q++) PB[q] = ps.kept(q) ? buf[ps.pos(q) * 64 + lane] : 0u;
+    wait_lgkm();
+    constexpr u32 KEEP = K16 ? K16 : 0xFFFFu;
+    if (roll < 0) dma_board(st.start_board + off, buf, lane);
+    else pool_dma<KEEP>(fx.pool, rec(V, R_LI), buf, lane);
+    (void)mux_edits(PB, ne, eidx, eval, lane);
+    // held: changed cells that held a plane a change clears but never sets
+    u32 cb[2], held[2];
+    rule_planes(PB, cb, Geo64<SPAWN_PHILOX>{lane, ssrc, 0, 0}, sc, 0u, held);
+    // (a lane mask, not two words held through the scores: such a lane stores those
+    // planes for every changed word)
+    const uint64_t held_lanes = __ballot((held[0] | held[1]) != 0u);
+    // the new plane 3 is read by the stores alone: computed here, or the compiler sinks
+    // it into them and keeps the rule's pair terms (eight registers) through the scores
+#pragma unroll
+    for (int w = 0; w < 2; w++) asm volatile("" : "+v"(PL(PB, 3, w)));
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- scores over the new board and goals
+    u32 PS[32];
+    wait_vm();
+    if (roll >= 0) {
+        pool_planes_lds<KEEP>(buf, roll >> 16, roll & 0xFFFF, lane, PS);
+    } else {
+        read_pairs(buf, lane, PS);
+        transpose32(PS);
+        // planes no board holds: no start board either (as pool_planes_lds has them), so
+        // neither path keeps a register for them
+#pragma unroll
+        for (int q = 0; q < 32; q++)
+            if (!((KEEP >> (q & 15)) & 1u)) PS[q] = 0u;
+    }
+    int pts, scr, pos, side;
+    score_planes(PB, gcol, PS, &pts, &scr, &pos, &side);
+    const ScoreTotals tot = score_totals(pts, scr, pos, side);
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- exits in the colour the epilogue gives them (update_exit_colors), then the
+    // plane words that changed (all of them on a step into plane mode)
+    const Words2 d9 = recolour_exits(
+        PB, can_exit_now(fl.min_performance(), tot.score, fl.baseline(), tot.possible));
+    u32 em[2] = {0u, 0u};           // the words the action's edits touched (this lane's)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (k < ne) {
+            const int y = eidx[k] >> 6, x = eidx[k] & 63;
+            const u32 bit = lane == 2 * (x >> 1) + (y >> 5) ? 1u << (y & 31) : 0u;
+            em[x & 1] |= bit;
+        }
+    }
+    u32 dw[2], dall[2];
+#pragma unroll
+    for (int w = 0; w < 2; w++) {
+        dw[w] = cb[w] | em[w];                       // words whose cells changed
+        dall[w] = em[w] | (((held_lanes >> lane) & 1ull) ? cb[w] : 0u);   // ... other planes
+    }
+    if (!pin || wave_or(dw[0] | dw[1] | d9.w[0] | d9.w[1])) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            if (!ps.kept(k)) continue;
+#pragma unroll
+            for (int w = 0; w < 2; w++) {
+                const u32 d = (k == 0 || k == 3 || k == 10 || k == 11) ? dw[w]
+                              : k == 9 ? (dw[w] | d9.w[w]) : dall[w];
+                if (!pin || d)
+                    __builtin_nontemporal_store(PL(PB, k, w), &bp[ps.pos(k + 16 * w) * 64]);
+            }
+        }
+    }
+    const int ok = gok | kPok64Board;
+    if (ok != pok_all && lane == 0) st.planes_ok[b] = ok;
+    if (OBS) {
+        const bool rw = kernarg().fx.obs_rw != 0;
+#pragma unroll
+        for (int w = 0; w < 2; w++) {
+            u32 g0 = gcol[0][w], g1 = gcol[1][w], g2 = gcol[2][w];
+            if (rw) {                                // white goals are background
+                const u32 wh = g0 & g1 & g2;
+                g0 &= ~wh;
+                g1 &= ~wh;
+                g2 &= ~wh;
+            }
+            const u32 b12 = PL(PB, 12, w), b13 = PL(PB, 13, w), b14 = PL(PB, 14, w);
+            u32 c = b12 & g0;
+            PL(PB, 12, w) = b12 ^ g0;
+            const u32 x13 = b13 ^ g1;
+            PL(PB, 13, w) = x13 ^ c;
+            c = (b13 & g1) | (c & x13);
+            const u32 x14 = b14 ^ g2;
+            PL(PB, 14, w) = x14 ^ c;
+            c = (b14 & g2) | (c & x14);
+            PL(PB, 15, w) ^= c;                      // (the carry out of bit 15 drops)
+        }
+        transpose32(PB);
+        lds_put_board(buf, lane, PB);               // (the start planes have been read)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        if (OBS >= 2) write_obs_channels<obs_esz(OBS)>(buf, vm, fl, b, lane);
+        else write_obs(buf, fx, fl, b, lane);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    int reset = 0;
+    if (lane == 0)
+        reset = epilogue_core(st, a, b, fl, act_reward, tot.points, tot.score, tot.possible,
+                              tot.side, ka.reward_out, ka.done_out, ka.flags_out, ka.ep_len_out,
+                              ka.ep_rew_out);
+    reset = __builtin_amdgcn_readfirstlane(reset);
+    if (fx.fuse_reset && reset && lane == 0) queue_reset(fx.scratch, st.B, a.step, b);

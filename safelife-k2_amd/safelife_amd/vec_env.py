@@ -125,8 +125,11 @@ class SafeLifeVecEnv:
         if stream_ring not in ("auto", "doubles"):
             raise ValueError("stream_ring must be 'auto' or 'doubles'")
         self.stream_ring = stream_ring
-        # where a 128x128 step leaves the board (sl_env_cfg.board_mode): "planes" keeps
-        # it in bit planes whenever the kernel can (a `board` read then completes the
+        # where a 64x64 or 128x128 step leaves the board (sl_env_cfg.board_mode): "planes"
+        # keeps it in bit planes whenever the kernel can -- at 64x64 on Philox steps
+        # without views, with packed views and with channel views (output_channels=(...),
+        # any obs_dtype; up to 64x64 and 1094 cells, 16-byte aligned output), which the
+        # step kernel writes from the planes -- (a `board` read then completes the
         # uint16 tensor first); "uint16" has every step write the changed rows; "auto"
         # is "planes" unless `board` was read within the last BOARD_READ_WINDOW steps --
         # a caller reading the board after every step (info['board'],
@@ -211,7 +214,8 @@ class SafeLifeVecEnv:
         self.board_planes = None
         if (H, W) == (64, 64):
             # the 64x64 board's planes share the goals mirror's tensor (half 0; the goals
-            # use half 1): board_planes == planes selects plane mode (sl_bits.hip)
+            # use half 1): board_planes == planes selects plane mode (sl_bits.hip), which
+            # steps with packed or channel views keep
             self.board_planes = self.planes
             s.board_planes = self.planes.data_ptr()
             s.board_zero = self._zero_planes(self._pool_bits(self.pool))
