@@ -525,19 +525,20 @@ class OracleEnv:
         # MovementBonusWrapper
         bonus, power, n = self.mb
         x0, y0 = self.agent_loc
-        if len(self.prior) >= n:
-            p1 = self.prior[-n]
-            dist = abs(x0 - p1[0]) + abs(y0 - p1[1])
-        elif len(self.prior) > 0:
-            p1 = self.prior[0]
-            dist = abs(x0 - p1[0]) + abs(y0 - p1[1]) + n - len(self.prior)
-        else:
-            dist = n
-        speed = dist / n
-        reward = reward + bonus * speed ** power
-        self.prior.append(self.agent_loc)
-        if len(self.prior) > n:
-            self.prior.pop(0)
+        if n:                               # (period 0: the batch's "no bonus" setting)
+            if len(self.prior) >= n:
+                p1 = self.prior[-n]
+                dist = abs(x0 - p1[0]) + abs(y0 - p1[1])
+            elif len(self.prior) > 0:
+                p1 = self.prior[0]
+                dist = abs(x0 - p1[0]) + abs(y0 - p1[1]) + n - len(self.prior)
+            else:
+                dist = n
+            speed = dist / n
+            reward = reward + bonus * speed ** power
+            self.prior.append(self.agent_loc)
+            if len(self.prior) > n:
+                self.prior.pop(0)
         # SimpleSideEffectPenalty
         side = side_effect_count(self.board, self.init_board, self.goals, self.exit_mask)
         reward = reward - (side - self.last_side_effect) * self.penalty_coef
@@ -586,7 +587,7 @@ class OracleEnv:
         period = self.mb[2]
         ln, hd = int(s["prior_len"]), int(s["prior_head"])
         self.prior = [(int(s["prior_x"][(hd + k) % period]), int(s["prior_y"][(hd + k) % period]))
-                      for k in range(ln)]
+                      for k in range(ln if period else 0)]
         self.episodes = int(s["episodes"])
         self.step_counter = int(step_counter)
 

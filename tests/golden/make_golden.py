@@ -27,9 +27,13 @@ Fixtures and synthetic level pools (§8(d)):
   traj_nav128_*.npz              G4 at 128x128: PPO-chain trajectories on C5 levels
   g7_ppo_loop_*.npz              G7: the PPO rollout loop (ppo.py:436-452), 16 envs,
                                  action draws and spawn refills in one global stream
+  feat_<name>.npz                G8: PPO-chain trajectories on synthetic non-square
+                                 levels with several exits, toggles on, other bonus
+                                 periods and views (group "feat"; levels built by
+                                 tests/feature_pools.py, stored in the fixture)
 
 Usage: python tests/golden/make_golden.py [--only g1,g2,traj,dens,pools,pool128,
-                                                  g1_128,g2_128,traj128,g7]
+                                                  g1_128,g2_128,traj128,g7,feat]
 """
 import argparse
 import hashlib
@@ -311,8 +315,38 @@ TRAJ128_SPECS = [
 ]
 
 
+# G8: what the other trajectories hold fixed.  Synthetic levels (kind "feature": seed,
+# H, W, exit count and build_level keywords of tests/feature_pools.py); toggles set on
+# the game object, bonus period / view / remove_white_goals through the reference's
+# constructors.  cfg_extra = [can_toggle_powers, can_toggle_colors, movement_bonus_period,
+# remove_white_goals].
+FEAT_SPECS = [
+    ("13x22_toggles", ("feature", (101, 13, 22, 3), dict(variant=1, n_crates=8, n_walls=8,
+                                                         n_life=16, n_spawners=2, n_targets=8)),
+     dict(steps=300, penalty=0.7, min_perf=-1.0, seed=21, view=(15, 15), time_limit=40,
+          seek=0.4, toggles=True, bonus_period=1)),
+    ("21x9_exits8", ("feature", (102, 21, 9, 8), dict(variant=3, n_crates=6, n_walls=6,
+                                                      n_life=10, n_spawners=0, n_targets=0)),
+     dict(steps=300, penalty=1.0, min_perf=-1.0, seed=22, view=(33, 33), time_limit=60,
+          seek=0.85, bonus_period=16, remove_white=False)),
+    ("10x10_view8x12", ("feature", (103, 10, 10, 2), dict(variant=0, n_crates=5, n_walls=4,
+                                                          n_life=8, n_spawners=1, n_targets=6)),
+     dict(steps=300, penalty=0.5, min_perf=0.01, seed=23, view=(8, 12), time_limit=50,
+          seek=0.2, toggles=True, bonus_period=3)),
+]
+
+
 def load_level_data(src):
     kind, path, idx = src
+    if kind == "feature":
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        sys.path.insert(0, os.path.join(REPO, "safelife-k2_amd"))
+        sys.path.insert(0, os.path.join(REPO, "oracle"))
+        import feature_pools
+        seed, H, W, n_exits = path
+        d = feature_pools.build_level(np.random.RandomState(seed), H, W, n_exits, **idx)
+        d["class"] = "safelife.safelife_game.SafeLifeGame"
+        return d
     if kind == "npz":
         d = np.load(os.path.join(REF, "safelife/levels", path))
         return {k: d[k] for k in d.files}
@@ -345,7 +379,8 @@ def _seek_action(game, rng):
     return int(rng.choice(opts))
 
 
-def run_traj(name, src, steps, penalty, min_perf, seed, view, time_limit=1000, seek=0.0):
+def run_traj(name, src, steps, penalty, min_perf, seed, view, time_limit=1000, seek=0.0,
+             toggles=False, bonus_period=None, remove_white=None, prefix="traj_"):
     from safelife import speedups
     from safelife.safelife_env import SafeLifeEnv
     from safelife.safelife_game import SafeLifeGame
@@ -356,10 +391,15 @@ def run_traj(name, src, steps, penalty, min_perf, seed, view, time_limit=1000, s
 
     def level_iter():
         while True:
-            yield SafeLifeGame.loaddata(level_data)
+            game = SafeLifeGame.loaddata(level_data)
+            if toggles:
+                game.can_toggle_powers = game.can_toggle_colors = True
+            yield game
 
-    env0 = SafeLifeEnv(level_iter(), view_shape=view, time_limit=time_limit)
-    env = ew.MovementBonusWrapper(env0)
+    env_kw = {} if remove_white is None else {"remove_white_goals": remove_white}
+    env0 = SafeLifeEnv(level_iter(), view_shape=view, time_limit=time_limit, **env_kw)
+    bonus_kw = {} if bonus_period is None else {"movement_bonus_period": bonus_period}
+    env = ew.MovementBonusWrapper(env0, **bonus_kw)
     env = ew.SimpleSideEffectPenalty(env, penalty_coef=penalty, min_performance=min_perf)
     env = ew.ContinuingEnv(env)
     speedups.seed(seed)                       # the spawn stream: RandomState(seed)
@@ -417,7 +457,10 @@ def run_traj(name, src, steps, penalty, min_perf, seed, view, time_limit=1000, s
     for k in ("board", "goals", "agent_loc", "orientation", "spawn_prob", "min_performance"):
         out["level_" + k] = np.asarray(level_data[k])
     out["cfg"] = np.array([penalty, min_perf, seed, view[0], view[1], time_limit], np.float64)
-    path = os.path.join(HERE, "traj_%s.npz" % name)
+    if prefix != "traj_":
+        out["cfg_extra"] = np.array([toggles, toggles, env.env.env.movement_bonus_period,
+                                     env0.remove_white_goals], np.int64)
+    path = os.path.join(HERE, "%s%s.npz" % (prefix, name))
     np.savez_compressed(path, **out)
     print("traj", name, "steps", steps, "dones", int(out["done"].sum()),
           "game_overs", int(out["game_over"].sum()), "->", os.path.basename(path))
@@ -620,6 +663,9 @@ def main():
     if "g7" in only:
         for name, src, kw in G7_SPECS:
             run_ppo_loop(name, src, **kw)
+    if "feat" in only:
+        for name, src, kw in FEAT_SPECS:
+            run_traj(name, src, prefix="feat_", **kw)
 
 
 if __name__ == "__main__":

@@ -112,6 +112,112 @@ def test_g3_trajectory(path):
         assert env.last_side_effect == d["side_effect"][t], ctx
 
 
+def _feat_files():
+    return sorted(glob.glob(os.path.join(GOLDEN, "feat_*.npz")))
+
+
+def make_feat_oracle_env(d, cls=oracle.OracleEnv):
+    env = make_oracle_env(d)
+    powers, colors, period, remove_white = (int(v) for v in d["cfg_extra"])
+    kw = dict(time_limit=env.time_limit, view_shape=env.view_shape, output_channels=None,
+              penalty_coef=env.penalty_coef, min_performance=env.wrapper_min_performance,
+              rng="stream", stream=env.stream, movement_bonus_period=period,
+              remove_white_goals=bool(remove_white), can_toggle_powers=bool(powers),
+              can_toggle_colors=bool(colors))
+    return cls(env.level_fn, **kw)
+
+
+def _check_traj_step(env, d, t, obs, r, done, info, ctx):
+    assert r == d["reward"][t], ctx          # bit-exact float64
+    assert done == d["done"][t], ctx
+    assert info["times_up"] == d["times_up"][t], ctx
+    assert tuple(env.agent_loc) == tuple(d["agent_loc"][t]), ctx
+    assert env.orientation == d["orientation"][t], ctx
+    assert np.array_equal(env.board, d["board"][t]), ctx
+    assert np.array_equal(env.goals, d["goals"][t]), ctx
+    assert np.array_equal(obs, d["obs"][t]), ctx
+    assert env.old_points == d["points"][t], ctx
+    assert env.last_side_effect == d["side_effect"][t], ctx
+
+
+@pytest.mark.parametrize("path", _feat_files(), ids=lambda p: os.path.basename(p)[5:-4])
+def test_g8_feature_trajectory(path):
+    """Reference-captured trajectories on what the traj_* fixtures hold fixed: H != W,
+    3 / 8 / 2 exits (np.nonzero order, two exits clipped to one view cell, all exits
+    recoloured), toggles on, bonus periods 1 / 16 / 3, remove_white_goals off, an even
+    non-square view and a view wider than twice the board.  The oracle follows the
+    reference stream; every recorded quantity at every step."""
+    d = np.load(path)
+    assert len(_feat_files()) == 3
+    env = make_feat_oracle_env(d)
+    obs = env.reset()
+    assert np.array_equal(obs, d["obs0"])
+    for t in range(len(d["action"])):
+        obs, r, done, info = env.step(int(d["action"][t]))
+        ctx = (os.path.basename(path), t)
+        _check_traj_step(env, d, t, obs, r, done, info, ctx)
+        assert tuple(env._perf_ratio()) == tuple(d["perf"][t]), ctx
+
+
+def test_g8_feature_trajectories_exercise_their_features():
+    """The fixtures hold what they are for: game-over and time-limit resets, toggles that
+    change the agent's power and colour bits, two exits clipped to one view cell, crates
+    moved across the seam, an exit refused by can_exit."""
+    import feature_pools
+    seen = {}
+    for path in _feat_files():
+        d = np.load(path)
+        env = make_feat_oracle_env(d, cls=feature_pools.TracingOracleEnv)
+        env.reset()
+        for a in d["action"]:
+            env.step(int(a))
+        seen[os.path.basename(path)[5:-4]] = (env.n, int(d["game_over"].sum()),
+                                              int(d["times_up"].sum()))
+    n, go, tu = seen["13x22_toggles"]
+    assert tu >= 2 and n["toggle_power"] >= 1 and n["toggle_color"] >= 1, seen
+    assert n["clipped_same"] >= 1 and n["push_seam"] >= 1, seen
+    # (a 33x33 view holds every cell of a 21x9 board: its exits are always in view)
+    n, go, tu = seen["21x9_exits8"]
+    assert go >= 5 and n["exit_in_view"] >= 1 and n["pull_seam"] >= 1, seen
+    n, go, tu = seen["10x10_view8x12"]
+    assert go >= 1 and tu >= 1 and n["toggle_power"] >= 1 and n["toggle_color"] >= 1, seen
+    assert n["can_exit_false"] >= 1, seen
+
+
+def test_g8_cpu_batch_follows_reference_trajectory():
+    """CpuBatch (sl_cpu_step.c) against the reference fixture itself where it can: the
+    21x9 level has 8 exits and no spawner, so no uniform is ever drawn and the Philox-only
+    CpuBatch replays the reference's trajectory (view 33x33, bonus period 16,
+    remove_white_goals off).  CpuBatch's config takes neither can_toggle_powers nor
+    can_toggle_colors and has no replay stream, so the two toggle fixtures (whose levels
+    spawn) are out of its reach; its other settings meet the oracle in
+    tests/test_feature_matrix_cpu.py."""
+    d = np.load(os.path.join(GOLDEN, "feat_21x9_exits8.npz"))
+    assert not ((d["level_board"] | d["level_goals"]) & oracle.SPAWNING).any()
+    penalty, min_perf, seed, vh, vw, time_limit = d["cfg"]
+    powers, colors, period, remove_white = (int(v) for v in d["cfg_extra"])
+    assert not powers and not colors
+    lvl = oracle.Level(d["level_board"], d["level_goals"], d["level_agent_loc"],
+                       d["level_orientation"], d["level_spawn_prob"], d["level_min_performance"])
+    cb = oracle.CpuBatch([lvl], 1, time_limit=int(time_limit), view_shape=(int(vh), int(vw)),
+                         remove_white_goals=bool(remove_white), movement_bonus_period=period,
+                         penalty_coef=float(penalty), min_performance=float(min_perf), obs=True)
+    cb.reset()
+    for t in range(len(d["action"])):
+        o, r, dn = cb.step(np.array([d["action"][t]], np.int32), threads=1)
+        ctx = t
+        assert r[0] == d["reward"][t], ctx
+        assert bool(dn[0]) == bool(d["done"][t]), ctx
+        assert np.array_equal(cb.board(0), d["board"][t]), ctx
+        assert np.array_equal(cb.board(0, 1), d["goals"][t]), ctx
+        assert np.array_equal(o[0], d["obs"][t]), ctx
+        s = cb.scalars(0)
+        assert (s["agent_x"], s["agent_y"]) == tuple(d["agent_loc"][t]), ctx
+        assert s["orientation"] == d["orientation"][t], ctx
+        assert s["old_points"] == d["points"][t], ctx
+        assert s["side_effect"] == d["side_effect"][t], ctx
+
+
 def test_obs_channels_match_packed():
     d = np.load(_traj_files()[0])
     env = make_oracle_env(d)
