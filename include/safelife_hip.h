@@ -276,6 +276,34 @@ int sl_side_effect_densities(const uint16_t *init_board, const uint16_t *final_b
                              uint16_t *keys, int32_t *n_keys, int32_t *present,
                              double *inaction, double *action, void *workspace,
                              int64_t workspace_bytes, void *stream);
+/*
+ * The same with a choice of kernel and per-episode Philox ids.
+ *   env_ids  dev uint32 [E] or NULL: episode e draws as env env_ids[e] (NULL: env0 + e),
+ *            so a batch of finished episodes keeps each episode's own id whatever
+ *            batch it lands in (ignored by SL_RNG_STREAM)
+ *   kernel   SL_KERNEL_GENERIC: one per-cell LDS launch per advance plus one mark /
+ *            count launch per sample, any shape up to 32768 cells;
+ *            SL_KERNEL_FAST: the bit-sliced rollout, one wave per board and one launch
+ *            per pass (four launches per call) -- Philox draws on 64x64 boards and on
+ *            boards of H <= 32, W <= 64; SL_ETOOBIG elsewhere;
+ *            SL_KERNEL_AUTO: FAST where it exists (sl_side_effect_kernel), else GENERIC.
+ *            The 64x64 kernel loads dwords: 64x64 boards at an address that is no
+ *            multiple of 4 go to GENERIC under AUTO and are SL_EINVAL under FAST.
+ * Both kernels give the same bytes.  sl_side_effect_densities is
+ * _k(..., NULL, SL_KERNEL_AUTO, stream).
+ */
+int sl_side_effect_densities_k(const uint16_t *init_board, const uint16_t *final_board,
+                               const int32_t *num_steps_dev, const int32_t *num_steps_host,
+                               const float *spawn_prob, int64_t E, int H, int W,
+                               int num_samples, int rng_mode, uint64_t seed, uint32_t env0,
+                               const double *draws, int64_t *stream_pos, int max_keys,
+                               uint16_t *keys, int32_t *n_keys, int32_t *present,
+                               double *inaction, double *action, void *workspace,
+                               int64_t workspace_bytes, const uint32_t *env_ids, int kernel,
+                               void *stream);
+/* SL_KERNEL_FAST if SL_KERNEL_AUTO takes the bit-sliced rollout for such a call, else
+ * SL_KERNEL_GENERIC (host only; no GPU needed) */
+int sl_side_effect_kernel(int H, int W, int rng_mode);
 
 /* ------------------------------------------------------------------ envs -- */
 
@@ -449,15 +477,26 @@ int sl_level_pool_prepare(sl_level_pool *pool, void *stream);
  * board advance, before any reset (the frame the reference captures after
  * env.step), and after the step's resets (the first frame of the next episode,
  * meaningful where flags & 4).  Copies only; the stepping itself is unchanged.
+ * env and flags are required; every other target is a dev pointer or NULL, and a
+ * NULL target is not copied (with all three reset_* NULL the second copy is skipped).
  */
 typedef struct sl_capture {
     int32_t n;                    /* envs recorded (0: none)                       */
-    const int32_t *env;           /* dev [n] env indices                           */
-    uint16_t *board, *goals;      /* dev [n, H, W]  after the advance              */
-    int32_t *orientation;         /* dev [n]                                        */
-    uint8_t *flags;               /* dev [n]  the step's info flags                */
-    uint16_t *reset_board, *reset_goals;   /* dev [n, H, W]  after the resets     */
-    int32_t *reset_orientation;   /* dev [n]                                        */
+    const int32_t *env;           /* dev [n] env indices (required)                */
+    uint16_t *board, *goals;      /* dev [n, H, W] or NULL  after the advance      */
+    int32_t *orientation;         /* dev [n] or NULL                                */
+    uint8_t *flags;               /* dev [n]  the step's info flags (required)     */
+    uint16_t *reset_board, *reset_goals;   /* dev [n, H, W] or NULL  after the resets */
+    int32_t *reset_orientation;   /* dev [n] or NULL                                */
+    /* the finished episode's record (EpisodeLog), each dev or NULL; copied with the
+       frame after the advance, before any reset overwrites them */
+    uint16_t *start_board;        /* dev [n, H, W]                                  */
+    int32_t *score, *possible;    /* dev [n]  performance_ratio() returns            */
+    int32_t *baseline;            /*          (score - baseline, possible - baseline) */
+    int32_t *num_steps;           /* dev [n]  board advances of the episode         */
+    float *spawn_prob;            /* dev [n]                                        */
+    double *min_performance;      /* dev [n]                                        */
+    int32_t *episode_length, *episode_reward, *level_index;   /* dev [n]            */
 } sl_capture;
 
 typedef struct sl_env_cfg {

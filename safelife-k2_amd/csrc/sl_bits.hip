@@ -29,7 +29,7 @@
 // kernel (k_env_reset_list) resets exactly those, one wave each, so the step
 // kernel carries no reset code (128 VGPRs, 4 waves/SIMD, no spills).  The <true>
 // instantiation also writes the packed observation (write_obs, 130 VGPRs, 3 waves).
-#include "sl_bits.h"
+#include "sl_bits_geo.h"
 #include "sl_obs.h"
 
 using namespace sl;
@@ -43,43 +43,6 @@ constexpr int kMinWavesObs = 3;   // the same for the instantiations that write 
                                   // replay the reference stream
 
 constexpr int N = 64;        // rows = columns = lanes
-
-// Neighbourhood of the 64x64 layout: lane l holds columns 2j, 2j+1 (j = l >> 1) over
-// rows 32h .. 32h+31 (h = l & 1).  Column 2j - 1 is word 1 of lane l - 2 and column
-// 2j + 2 word 0 of lane l + 2 (the 64-lane rotation wraps at W = 64); the rows
-// around a word come from the other half's word (lane l ^ 1), which also supplies
-// the wrap at H = 64.
-template <int MODE>
-struct Geo64 {
-    int lane;
-    StreamSrc src;     // SPAWN_STREAM: the supplied uniforms; pos = this tensor's first
-    int64_t pos;
-    int count;         // SPAWN_COUNT: this lane's eligible cells
-    template <class F>
-    __device__ __forceinline__ V3 vert(const u32 *P, int w, F f) const {
-        const u32 x = f(P, w);
-        return vert_with(x, lane_x1(x));
-    }
-    __device__ __forceinline__ H3 horiz(u32 w0, u32 w1) const {
-        return H3{lane_m1(lane_m1(w1)), lane_p1(lane_p1(w0))};
-    }
-    __device__ __forceinline__ bool halo_spawn() const { return false; }
-    // the 2x2 spawn block of rows 32h + y, y + 1 (y even) of the lane's column pair
-    __device__ __forceinline__ u32 block(int y) const {
-        return (u32)(((32 * (lane & 1) + y) >> 1) * (N / 2) + (lane >> 1));
-    }
-    // spawners are rare on these boards: per-lane Philox draws, no LDS list
-    __device__ __forceinline__ void spawn(const u32 elig[2], u32 sp[2], const SpawnCtx &sc,
-                                          u32 tensor) {
-        if (MODE == SPAWN_PHILOX) {
-            philox_spawn(*this, elig, sp, sc, tensor);
-        } else if (MODE == SPAWN_STREAM) {
-            (void)stream_draws<true>(elig, sp, sc.thr, src, pos, lane);
-        } else {
-            count += __builtin_popcount(elig[0]) + __builtin_popcount(elig[1]);
-        }
-    }
-};
 
 // ---------------------------------------------------------------- LDS staging
 // A wave's 8 KiB LDS buffer holds one 64x64 board, row-major, with the 16-byte

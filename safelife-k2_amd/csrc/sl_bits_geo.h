@@ -1,0 +1,110 @@
+// sl_bits_geo.h -- the geometry policies of rule_planes (sl_bits.h) for the layouts more
+// than one file uses: Geo64 (64x64 boards: sl_bits.hip, sl_rollout_bits.hip) and
+// GeoSmall (boards up to 32 rows x 64 columns: sl_bits_small.hip, sl_rollout_bits.hip).
+#pragma once
+#include "sl_bits.h"
+
+namespace sl {
+namespace bits {
+
+// Neighbourhood of the 64x64 layout: lane l holds columns 2j, 2j+1 (j = l >> 1) over
+// rows 32h .. 32h+31 (h = l & 1).  Column 2j - 1 is word 1 of lane l - 2 and column
+// 2j + 2 word 0 of lane l + 2 (the 64-lane rotation wraps at W = 64); the rows
+// around a word come from the other half's word (lane l ^ 1), which also supplies
+// the wrap at H = 64.
+template <int MODE>
+struct Geo64 {
+    static constexpr int N = 64;        // rows = columns = lanes
+    int lane;
+    StreamSrc src;     // SPAWN_STREAM: the supplied uniforms; pos = this tensor's first
+    int64_t pos;
+    int count;         // SPAWN_COUNT: this lane's eligible cells
+    template <class F>
+    __device__ __forceinline__ V3 vert(const u32 *P, int w, F f) const {
+        const u32 x = f(P, w);
+        return vert_with(x, lane_x1(x));
+    }
+    __device__ __forceinline__ H3 horiz(u32 w0, u32 w1) const {
+        return H3{lane_m1(lane_m1(w1)), lane_p1(lane_p1(w0))};
+    }
+    __device__ __forceinline__ bool halo_spawn() const { return false; }
+    // the 2x2 spawn block of rows 32h + y, y + 1 (y even) of the lane's column pair
+    __device__ __forceinline__ u32 block(int y) const {
+        return (u32)(((32 * (lane & 1) + y) >> 1) * (N / 2) + (lane >> 1));
+    }
+    // spawners are rare on these boards: per-lane Philox draws, no LDS list
+    __device__ __forceinline__ void spawn(const u32 elig[2], u32 sp[2], const SpawnCtx &sc,
+                                          u32 tensor) {
+        if (MODE == SPAWN_PHILOX) {
+            philox_spawn(*this, elig, sp, sc, tensor);
+        } else if (MODE == SPAWN_STREAM) {
+            (void)stream_draws<true>(elig, sp, sc.thr, src, pos, lane);
+        } else {
+            count += __builtin_popcount(elig[0]) + __builtin_popcount(elig[1]);
+        }
+    }
+};
+
+// Boards up to 32 rows x 64 columns: lane j < nl = ceil(W / 2) holds the column pair
+// (2j, 2j+1) over all rows.  Vertical neighbours are rotations within the low H bits,
+// horizontal ones come through ds_bpermute, which wraps at W for any W; for odd W the
+// last lane's second word is a copy of column 0.
+template <int MODE>
+struct GeoSmall {
+    int lane, H, W, nl;
+    u32 mh;                  // the low H bits
+    int src_l, src_r;        // lanes holding columns 2j - 1 and 2j + 2
+    bool odd_last;           // this lane's word 1 is the column-0 copy (odd W)
+    StreamSrc src;           // SPAWN_STREAM: the supplied uniforms from this tensor's first
+    int64_t pos;
+    int count;               // SPAWN_COUNT: this lane's eligible cells
+    template <class F>
+    __device__ __forceinline__ V3 vert(const u32 *P, int w, F f) const {
+        const u32 x = f(P, w);
+        return V3{((x << 1) | (x >> (H - 1))) & mh, ((x >> 1) | ((x & 1u) << (H - 1))) & mh};
+    }
+    __device__ __forceinline__ H3 horiz(u32 w0, u32 w1) const {
+        const u32 right_col = odd_last ? w0 : w1;          // this lane's last real column
+        return H3{(u32)__builtin_amdgcn_ds_bpermute(4 * src_l, (int)right_col),
+                  (u32)__builtin_amdgcn_ds_bpermute(4 * src_r, (int)w0)};
+    }
+    __device__ __forceinline__ bool halo_spawn() const { return false; }
+    // the 2x2 spawn block of rows y, y + 1 (y even) of the lane's column pair
+    __device__ __forceinline__ u32 block(int y) const { return (u32)((y >> 1) * nl + lane); }
+    // (the column-0 copy's draws are discarded with the rest of that word; in replay
+    // mode it draws nothing, so it cannot shift the real cells' ranks)
+    __device__ __forceinline__ void spawn(const u32 elig[2], u32 sp[2], const SpawnCtx &sc,
+                                          u32 tensor) {
+        const u32 e[2] = {elig[0], odd_last ? 0u : elig[1]};
+        if (MODE == SPAWN_PHILOX) {
+            philox_spawn(*this, elig, sp, sc, tensor);
+        } else if (MODE == SPAWN_STREAM) {
+            (void)stream_draws<false>(e, sp, sc.thr, src, pos, lane);
+        } else {
+            count += __builtin_popcount(e[0]) + __builtin_popcount(e[1]);
+        }
+    }
+};
+
+// the geometry of lane `lane` on an H x W board (lanes >= ceil(W / 2) hold nothing)
+template <int MODE>
+__device__ __forceinline__ GeoSmall<MODE> small_geo(int lane, int H, int W) {
+    GeoSmall<MODE> g;
+    const int nl = (W + 1) >> 1;
+    const bool active = lane < nl;
+    g.lane = lane;
+    g.H = H;
+    g.W = W;
+    g.nl = nl;
+    g.mh = H == 32 ? ~0u : ((1u << H) - 1u);
+    g.src_l = active ? (lane == 0 ? nl - 1 : lane - 1) : lane;
+    g.src_r = active ? (lane + 1 == nl ? 0 : lane + 1) : lane;
+    g.odd_last = (W & 1) && lane == nl - 1;
+    g.src = StreamSrc{nullptr, 0, nullptr};
+    g.pos = 0;
+    g.count = 0;
+    return g;
+}
+
+}  // namespace bits
+}  // namespace sl

@@ -23,7 +23,7 @@
 // Finished envs are reset by their own wave at the end of the step (small_reset).
 // Philox draws, or the reference's stream order after a replay prologue
 // (k_stream_prologue_small).
-#include "sl_bits.h"
+#include "sl_bits_geo.h"
 
 using namespace sl;
 using namespace sl::fast;
@@ -32,63 +32,6 @@ using namespace sl::bits;
 namespace {
 
 constexpr int kMaxH = 32, kMaxW = 64;
-
-template <int MODE>
-struct GeoSmall {
-    int lane, H, W, nl;
-    u32 mh;                  // the low H bits
-    int src_l, src_r;        // lanes holding columns 2j - 1 and 2j + 2
-    bool odd_last;           // this lane's word 1 is the column-0 copy (odd W)
-    StreamSrc src;           // SPAWN_STREAM: the supplied uniforms from this tensor's first
-    int64_t pos;
-    int count;               // SPAWN_COUNT: this lane's eligible cells
-    template <class F>
-    __device__ __forceinline__ V3 vert(const u32 *P, int w, F f) const {
-        const u32 x = f(P, w);
-        return V3{((x << 1) | (x >> (H - 1))) & mh, ((x >> 1) | ((x & 1u) << (H - 1))) & mh};
-    }
-    __device__ __forceinline__ H3 horiz(u32 w0, u32 w1) const {
-        const u32 right_col = odd_last ? w0 : w1;          // this lane's last real column
-        return H3{(u32)__builtin_amdgcn_ds_bpermute(4 * src_l, (int)right_col),
-                  (u32)__builtin_amdgcn_ds_bpermute(4 * src_r, (int)w0)};
-    }
-    __device__ __forceinline__ bool halo_spawn() const { return false; }
-    // the 2x2 spawn block of rows y, y + 1 (y even) of the lane's column pair
-    __device__ __forceinline__ u32 block(int y) const { return (u32)((y >> 1) * nl + lane); }
-    // (the column-0 copy's draws are discarded with the rest of that word; in replay
-    // mode it draws nothing, so it cannot shift the real cells' ranks)
-    __device__ __forceinline__ void spawn(const u32 elig[2], u32 sp[2], const SpawnCtx &sc,
-                                          u32 tensor) {
-        const u32 e[2] = {elig[0], odd_last ? 0u : elig[1]};
-        if (MODE == SPAWN_PHILOX) {
-            philox_spawn(*this, elig, sp, sc, tensor);
-        } else if (MODE == SPAWN_STREAM) {
-            (void)stream_draws<false>(e, sp, sc.thr, src, pos, lane);
-        } else {
-            count += __builtin_popcount(e[0]) + __builtin_popcount(e[1]);
-        }
-    }
-};
-
-// the geometry of lane `lane` on an H x W board (lanes >= ceil(W / 2) hold nothing)
-template <int MODE>
-__device__ __forceinline__ GeoSmall<MODE> small_geo(int lane, int H, int W) {
-    GeoSmall<MODE> g;
-    const int nl = (W + 1) >> 1;
-    const bool active = lane < nl;
-    g.lane = lane;
-    g.H = H;
-    g.W = W;
-    g.nl = nl;
-    g.mh = H == 32 ? ~0u : ((1u << H) - 1u);
-    g.src_l = active ? (lane == 0 ? nl - 1 : lane - 1) : lane;
-    g.src_r = active ? (lane + 1 == nl ? 0 : lane + 1) : lane;
-    g.odd_last = (W & 1) && lane == nl - 1;
-    g.src = StreamSrc{nullptr, 0, nullptr};
-    g.pos = 0;
-    g.count = 0;
-    return g;
-}
 
 typedef __attribute__((address_space(3))) u32 lds_u32;
 typedef __attribute__((address_space(3))) const uint16_t lds_cu16;

@@ -12,6 +12,7 @@
 // board: cells are visited in 256-cell chunks in row-major order and ranked by a
 // ballot/popcount prefix within each wave plus a 4-entry cross-wave prefix.
 #include "sl_device.h"
+#include "sl_rollout_bits.h"
 #include "../../include/safelife_hip.h"
 
 using namespace sl;
@@ -222,7 +223,8 @@ __global__ void __launch_bounds__(NT)
 k_rollout_advance(const uint16_t *__restrict__ in, uint16_t *__restrict__ out, int H, int W,
                   const int32_t *__restrict__ steps, int S, int it,
                   const float *__restrict__ spawn_prob, uint64_t seed, uint32_t env0,
-                  const double *__restrict__ draws, const int64_t *__restrict__ offsets) {
+                  const uint32_t *__restrict__ env_ids, const double *__restrict__ draws,
+                  const int64_t *__restrict__ offsets) {
     extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
     __shared__ int wave_tot[NT / 64];
     const int hw = H * W;
@@ -258,7 +260,8 @@ k_rollout_advance(const uint16_t *__restrict__ in, uint16_t *__restrict__ out, i
             pos += tot;
         } else if (elig) {
             const int y = i / W;
-            u = spawn_uniform(y, i - y * W, W, env0 + (uint32_t)e, t, 4u + (uint32_t)which, seed);
+            u = spawn_uniform(y, i - y * W, W, env_ids ? env_ids[e] : env0 + (uint32_t)e, t,
+                              4u + (uint32_t)which, seed);
         }
         if (elig && u < thr) r = sv;
         if (i < hw) dst[i] = (uint16_t)r;
@@ -458,6 +461,11 @@ extern "C" int sl_side_effect_workspace(int64_t E, int H, int W, int64_t *bytes)
     return SL_OK;
 }
 
+extern "C" int sl_side_effect_kernel(int H, int W, int rng_mode) {
+    return (rng_mode == SL_RNG_PHILOX && rollout_bits_shape(H, W)) ? SL_KERNEL_FAST
+                                                                   : SL_KERNEL_GENERIC;
+}
+
 extern "C" int sl_side_effect_densities(const uint16_t *init_board, const uint16_t *final_board,
                                         const int32_t *num_steps_dev,
                                         const int32_t *num_steps_host,
@@ -468,18 +476,50 @@ extern "C" int sl_side_effect_densities(const uint16_t *init_board, const uint16
                                         int32_t *n_keys, int32_t *present, double *inaction,
                                         double *action, void *workspace,
                                         int64_t workspace_bytes, void *stream) {
+    return sl_side_effect_densities_k(init_board, final_board, num_steps_dev, num_steps_host,
+                                      spawn_prob, E, H, W, num_samples, rng_mode, seed, env0,
+                                      draws, stream_pos, max_keys, keys, n_keys, present,
+                                      inaction, action, workspace, workspace_bytes, nullptr,
+                                      SL_KERNEL_AUTO, stream);
+}
+
+extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
+                                          const uint16_t *final_board,
+                                          const int32_t *num_steps_dev,
+                                          const int32_t *num_steps_host,
+                                          const float *spawn_prob, int64_t E, int H, int W,
+                                          int num_samples, int rng_mode, uint64_t seed,
+                                          uint32_t env0, const double *draws,
+                                          int64_t *stream_pos, int max_keys, uint16_t *keys,
+                                          int32_t *n_keys, int32_t *present, double *inaction,
+                                          double *action, void *workspace,
+                                          int64_t workspace_bytes, const uint32_t *env_ids,
+                                          int kernel, void *stream) {
+    if (kernel != SL_KERNEL_AUTO && kernel != SL_KERNEL_GENERIC && kernel != SL_KERNEL_FAST)
+        return SL_EINVAL;
     if (E < 0 || H < 2 || W < 2 || num_samples < 1 || max_keys < 1 || max_keys > 1024)
         return SL_EINVAL;
     if ((int64_t)H * W > kMaxBoardCells) return SL_ETOOBIG;
     if (rng_mode != SL_RNG_STREAM && rng_mode != SL_RNG_PHILOX) return SL_EINVAL;
     if (rng_mode == SL_RNG_STREAM && (E > 1 || !draws || !stream_pos)) return SL_EINVAL;
     if (E == 0) return SL_OK;
+    if (2 * E > 0x7FFFFFFF) return SL_EINVAL;
     if (!init_board || !final_board || !num_steps_dev || !num_steps_host || !spawn_prob ||
         !keys || !n_keys || !present || !inaction || !action || !workspace)
         return SL_EINVAL;
     int64_t need;
     sl_side_effect_workspace(E, H, W, &need);
     if (workspace_bytes < need) return SL_EINVAL;
+    // the bit-sliced rollout: Philox draws on 64x64 boards and boards up to 32 x 64.  Its
+    // 64x64 kernel loads dwords, so 64x64 boards at an address that is no multiple of 4
+    // go to the per-cell kernels (SL_KERNEL_FAST: SL_EINVAL); the small kernel reads uint16
+    bool fast = kernel != SL_KERNEL_GENERIC &&
+                sl_side_effect_kernel(H, W, rng_mode) == SL_KERNEL_FAST;
+    if (kernel == SL_KERNEL_FAST && !fast) return SL_ETOOBIG;
+    if (fast && H == 64 && ((((uintptr_t)init_board) | ((uintptr_t)final_board)) & 3)) {
+        if (kernel == SL_KERNEL_FAST) return SL_EINVAL;
+        fast = false;
+    }
     hipStream_t s = (hipStream_t)stream;
     const int hw = H * W;
     const int64_t nb = 2 * E;
@@ -493,13 +533,30 @@ extern "C" int sl_side_effect_densities(const uint16_t *init_board, const uint16
         if (num_steps_host[e] < 0) return SL_EINVAL;
         max_steps = num_steps_host[e] > max_steps ? num_steps_host[e] : max_steps;
     }
+    const int64_t map_elems = E * (int64_t)max_keys * hw;
+    if (fast) {
+        // four launches: mark, compact, count, normalise (sl_rollout_bits.hip); the mark
+        // pass writes every bitmap word, the boards stay where the caller has them
+        RolloutArgs ra{init_board, final_board, num_steps_dev, spawn_prob, env_ids, env0, seed,
+                       num_samples, H, W, bitmap, keys, n_keys, max_keys, inaction, action};
+        if (hipMemsetAsync(inaction, 0, map_elems * 8, s) != hipSuccess ||
+            hipMemsetAsync(action, 0, map_elems * 8, s) != hipSuccess)
+            return SL_EHIP;
+        if (launch_rollout_bits(ra, E, 0, s)) return SL_EHIP;
+        hipLaunchKernelGGL(k_density_compact, dim3((unsigned)E), dim3(NT), 0, s, bitmap, max_keys,
+                           keys, n_keys, present);
+        if (hipGetLastError() != hipSuccess) return SL_EHIP;
+        if (launch_rollout_bits(ra, E, 1, s)) return SL_EHIP;
+        hipLaunchKernelGGL(k_density_norm, dim3(1024), dim3(NT), 0, s, inaction, action,
+                           map_elems, (double)num_samples);
+        return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+    }
     const int iters = max_steps + num_samples;
     const size_t lds = (size_t)hw * sizeof(uint16_t);
     if (!lds_ok((const void *)k_rollout_advance<SL_RNG_STREAM>, lds) ||
         !lds_ok((const void *)k_rollout_advance<SL_RNG_PHILOX>, lds))
         return SL_ETOOBIG;
     const dim3 cell_grid((unsigned)((hw + NT - 1) / NT), (unsigned)nb);
-    const int64_t map_elems = E * (int64_t)max_keys * hw;
     if (hipMemsetAsync(bitmap, 0, nb * 2048 * 4, s) != hipSuccess ||
         hipMemsetAsync(inaction, 0, map_elems * 8, s) != hipSuccess ||
         hipMemsetAsync(action, 0, map_elems * 8, s) != hipSuccess)
@@ -532,11 +589,13 @@ extern "C" int sl_side_effect_densities(const uint16_t *init_board, const uint16
                 }
                 hipLaunchKernelGGL(k_rollout_advance<SL_RNG_STREAM>, dim3((unsigned)nb),
                                    dim3(NT), lds, s, cur, nxt, H, W, num_steps_dev, num_samples,
-                                   it, spawn_prob, seed, env0, draws, ri + 2);
+                                   it, spawn_prob, seed, env0, (const uint32_t *)nullptr, draws,
+                                   ri + 2);
             } else {
                 hipLaunchKernelGGL(k_rollout_advance<SL_RNG_PHILOX>, dim3((unsigned)nb),
                                    dim3(NT), lds, s, cur, nxt, H, W, num_steps_dev, num_samples,
-                                   it, spawn_prob, seed, env0, draws, (const int64_t *)nullptr);
+                                   it, spawn_prob, seed, env0, env_ids, draws,
+                                   (const int64_t *)nullptr);
             }
             uint16_t *t = cur;
             cur = nxt;

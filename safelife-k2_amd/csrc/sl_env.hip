@@ -1024,10 +1024,8 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
     fx.scratch = cfg->scratch;
     fx.ev_end = cfg->ev_end;
     const sl_capture *cap = (cfg->capture && cfg->capture->n > 0) ? cfg->capture : nullptr;
-    if (cap && (!cap->env || !cap->board || !cap->goals || !cap->orientation || !cap->flags ||
-                !cap->reset_board || !cap->reset_goals || !cap->reset_orientation ||
-                !info_flags || !cfg->auto_reset))
-        return SL_EINVAL;
+    // (env and flags are needed; every other target may be NULL and is then not copied)
+    if (cap && (!cap->env || !cap->flags || !info_flags || !cfg->auto_reset)) return SL_EINVAL;
     fx.capture = cap;
     fx.stream = replay ? 1 : 0;
     fx.stream_pos = cfg->stream_pos;
@@ -1184,16 +1182,35 @@ k_capture(sl_env_state st, sl_capture c, const uint8_t *__restrict__ flags, int 
     const int64_t b = c.env[i];
     if (b < 0 || b >= st.B) return;
     const int64_t hw = (int64_t)st.H * st.W;
-    uint16_t *ob = (phase ? c.reset_board : c.board) + i * hw;
-    uint16_t *og = (phase ? c.reset_goals : c.goals) + i * hw;
+    uint16_t *ob = phase ? c.reset_board : c.board;
+    uint16_t *og = phase ? c.reset_goals : c.goals;
     const uint16_t *sb = st.board + b * hw, *sg = st.goals + b * hw;
-    for (int64_t k = threadIdx.x; k < hw; k += NT) {
-        ob[k] = sb[k];
-        og[k] = sg[k];
+    if (ob)
+        for (int64_t k = threadIdx.x; k < hw; k += NT) ob[i * hw + k] = sb[k];
+    if (og)
+        for (int64_t k = threadIdx.x; k < hw; k += NT) og[i * hw + k] = sg[k];
+    // the episode's record, before a reset overwrites it (the step's epilogue has just
+    // written score / possible over the advanced board and goals: epilogue_core)
+    if (!phase && c.start_board) {
+        const uint16_t *ss = st.start_board + b * hw;
+        uint16_t *os = c.start_board + i * hw;
+        for (int64_t k = threadIdx.x; k < hw; k += NT) os[k] = ss[k];
     }
     if (threadIdx.x == 0) {
-        (phase ? c.reset_orientation : c.orientation)[i] = st.orientation[b];
-        if (!phase) c.flags[i] = flags[b];
+        int32_t *oo = phase ? c.reset_orientation : c.orientation;
+        if (oo) oo[i] = st.orientation[b];
+        if (!phase) {
+            c.flags[i] = flags[b];
+            if (c.score) c.score[i] = st.score[b];
+            if (c.possible) c.possible[i] = st.possible[b];
+            if (c.baseline) c.baseline[i] = st.baseline[b];
+            if (c.num_steps) c.num_steps[i] = st.num_steps[b];
+            if (c.spawn_prob) c.spawn_prob[i] = st.spawn_prob[b];
+            if (c.min_performance) c.min_performance[i] = st.min_performance[b];
+            if (c.episode_length) c.episode_length[i] = st.episode_length[b];
+            if (c.episode_reward) c.episode_reward[i] = st.episode_reward[b];
+            if (c.level_index) c.level_index[i] = st.level_index[b];
+        }
     }
 }
 
@@ -1201,6 +1218,7 @@ k_capture(sl_env_state st, sl_capture c, const uint8_t *__restrict__ flags, int 
 
 int sl::launch_capture(const sl_env_state &st, const sl_capture &c, const uint8_t *flags,
                        int phase, hipStream_t s) {
+    if (phase && !c.reset_board && !c.reset_goals && !c.reset_orientation) return SL_OK;
     hipLaunchKernelGGL(k_capture, dim3((unsigned)c.n), dim3(NT), 0, s, st, c, flags, phase);
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }

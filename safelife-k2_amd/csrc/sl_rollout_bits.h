@@ -1,0 +1,31 @@
+// sl_rollout_bits.h -- launcher of the bit-sliced side-effect rollout kernels
+// (sl_rollout_bits.hip), called by sl_side_effect_densities_k (sl_board.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace sl {
+
+struct RolloutArgs {
+    const uint16_t *init_board, *final_board;   // dev [E, H, W]
+    const int32_t *steps;                       // dev [E]
+    const float *spawn_prob;                    // dev [E]
+    const uint32_t *env_ids;                    // dev [E] or NULL: env0 + e
+    uint32_t env0;
+    uint64_t seed;
+    int32_t S, H, W;                            // S = num_samples
+    uint32_t *bitmap;                           // dev [2E][2048]: pass 0 writes every word
+    const uint16_t *keys;                       // pass 1: dev [E, max_keys] ascending
+    const int32_t *n_keys;                      // pass 1: dev [E]
+    int32_t max_keys;
+    double *inaction, *action;                  // pass 1: dev [E, max_keys, H, W] counts
+};
+
+// a bit-sliced rollout exists for this shape (Philox draws only)
+bool rollout_bits_shape(int H, int W);
+
+// pass 0: mark every sampled key; pass 1: count every sampled cell into its key's map.
+// One launch of 2E single-wave workgroups each.
+int launch_rollout_bits(const RolloutArgs &a, int64_t E, int pass, hipStream_t s);
+
+}  // namespace sl

@@ -26,4 +26,7 @@ def __getattr__(name):
     if name in ("SafeLifeEnv", "SafeLifeGame"):
         from . import env as _env
         return getattr(_env, name)
+    if name == "EpisodeLog":
+        from .episode_log import EpisodeLog
+        return EpisodeLog
     raise AttributeError(name)

@@ -81,7 +81,11 @@ class MT19937(ctypes.Structure):
 class Capture(ctypes.Structure):
     _fields_ = [("n", i32), ("env", vp), ("board", vp), ("goals", vp), ("orientation", vp),
                 ("flags", vp), ("reset_board", vp), ("reset_goals", vp),
-                ("reset_orientation", vp)]
+                ("reset_orientation", vp),
+                # the finished episode's record (EpisodeLog); NULL: not copied
+                ("start_board", vp), ("score", vp), ("possible", vp), ("baseline", vp),
+                ("num_steps", vp), ("spawn_prob", vp), ("min_performance", vp),
+                ("episode_length", vp), ("episode_reward", vp), ("level_index", vp)]
 
 
 _lib = None
@@ -127,6 +131,12 @@ def lib():
     L.sl_side_effect_densities.argtypes = [vp, vp, vp, vp, vp, i64, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, u64, u32, vp, vp,
                                            ctypes.c_int, vp, vp, vp, vp, vp, vp, i64, vp]
+    if hasattr(L, "sl_side_effect_densities_k") or LIB_PATH == _DEFAULT_LIB:
+        L.sl_side_effect_densities_k.argtypes = (L.sl_side_effect_densities.argtypes[:-1] +
+                                                 [vp, ctypes.c_int, vp])
+        L.sl_side_effect_densities_k.restype = ctypes.c_int
+        L.sl_side_effect_kernel.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.sl_side_effect_kernel.restype = ctypes.c_int
     L.sl_env_obs.argtypes = [ctypes.POINTER(EnvState), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                              ctypes.c_int, vp, ctypes.c_int, vp, vp]
     L.sl_sample_actions.argtypes = [vp, ctypes.c_int, i64, ctypes.c_int, i64, ctypes.c_int, vp,

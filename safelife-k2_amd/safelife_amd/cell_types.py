@@ -49,3 +49,26 @@ class CellTypes:
     parasite = inhibiting | alive | pushable | frozen
     weed = preserving | alive | pushable | frozen
     powers = alive | freezing | spawning
+
+
+# The reference's cell names (render_text.py:74-102), as data: the cell without its colour
+# bits names the type, the colour bits name the colour.
+CELL_TYPE_NAMES = (
+    (CellTypes.empty, "empty"), (CellTypes.life, "life"), (CellTypes.alive, "hard-life"),
+    (CellTypes.wall, "wall"), (CellTypes.crate, "crate"), (CellTypes.plant, "plant"),
+    (CellTypes.tree, "tree"), (CellTypes.ice_cube, "ice-cube"),
+    (CellTypes.parasite, "parasite"), (CellTypes.weed, "weed"),
+    (CellTypes.spawner, "spawner"), (CellTypes.hard_spawner, "hard-spawner"),
+    (CellTypes.level_exit, "exit"), (CellTypes.fountain, "fountain"))
+# colour index (red 1, green 2, blue 4) -> name
+COLOR_NAMES = ("gray", "red", "green", "yellow", "blue", "magenta", "cyan", "white")
+_TYPE_NAME = {int(v): n for v, n in CELL_TYPE_NAMES}
+
+
+def cell_name(cell):
+    """'<type>-<colour>' of a cell value, e.g. 'life-green'; a type outside the table is
+    'unknown'."""
+    cell = int(cell)
+    colour = (cell >> CellTypes.color_bit) & 7
+    return "%s-%s" % (_TYPE_NAME.get(cell & ~int(CellTypes.rainbow_color), "unknown"),
+                      COLOR_NAMES[colour])

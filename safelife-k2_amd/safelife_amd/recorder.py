@@ -41,6 +41,10 @@ class TrajectoryRecorder:
         if not venv.auto_reset:
             raise ValueError("TrajectoryRecorder needs auto_reset=True (episodes are cut "
                              "at the resets inside sl_env_step)")
+        from .episode_log import EpisodeLog
+        if isinstance(getattr(venv, "_recorder", None), EpisodeLog):
+            raise ValueError("an EpisodeLog is attached to this env (one TrajectoryRecorder "
+                             "or EpisodeLog at a time)")
         torch = venv.torch
         self.venv = venv
         self.video_name = video_name

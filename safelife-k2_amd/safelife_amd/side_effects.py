@@ -24,13 +24,20 @@ from . import _lib
 
 def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
                           rng="philox", seed=0, env0=0, spawn_stream=None, stream_pos=0,
-                          max_keys=64, device=None, return_stream_pos=False):
+                          max_keys=64, device=None, return_stream_pos=False, kernel="auto",
+                          env_ids=None):
     """Density maps of E episodes' counterfactual (inaction) and actual rollouts.
 
     init_boards, final_boards: [E, H, W] (numpy or torch) -- game._init_data['board']
     and game.board; num_steps: [E] ints (game.num_steps); spawn_prob: scalar or [E].
     rng: 'philox' (batched) or 'stream' (E == 1: the reference's draw order from the
     uniform stream ``spawn_stream`` starting at ``stream_pos``).
+    kernel: 'fast' requires the bit-sliced rollout (one wave per board, four launches per
+    call: Philox draws on 64x64 boards and boards of H <= 32, W <= 64; raises elsewhere),
+    'generic' the per-cell kernels (one launch per advance), 'auto' takes 'fast' where it
+    exists.  Both give the same bytes.
+    env_ids: [E] Philox env ids, one per episode (default env0 + e), so an episode draws
+    the same whatever batch it is scored in.
     Returns a list of (inaction, action) dicts, one per episode.
     """
     import torch
@@ -52,6 +59,14 @@ def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_
     sp = torch.as_tensor(np.broadcast_to(np.asarray(spawn_prob, dtype=np.float32), (E,)).copy(),
                          device=dev)
     mode = {"philox": _lib.SL_RNG_PHILOX, "stream": _lib.SL_RNG_STREAM}[rng]
+    kern = {"auto": _lib.SL_KERNEL_AUTO, "generic": _lib.SL_KERNEL_GENERIC,
+            "fast": _lib.SL_KERNEL_FAST}[kernel]
+    ids = None
+    if env_ids is not None:
+        ids_h = np.ascontiguousarray(np.asarray(env_ids, dtype=np.int64).reshape(-1))
+        if ids_h.shape != (E,) or (ids_h < 0).any() or (ids_h > 0xFFFFFFFF).any():
+            raise ValueError("env_ids must be %d ids in [0, 2**32)" % E)
+        ids = torch.from_numpy(ids_h.astype(np.uint32).view(np.int32)).to(dev)
     draws = pos = None
     if mode == _lib.SL_RNG_STREAM:
         if E != 1 or spawn_stream is None:
@@ -66,13 +81,13 @@ def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_
     nbytes = ctypes.c_int64()
     _lib.check(L.sl_side_effect_workspace(E, H, W, ctypes.byref(nbytes)), "workspace")
     ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-    _lib.check(L.sl_side_effect_densities(
+    _lib.check(L.sl_side_effect_densities_k(
         b0.data_ptr(), b1.data_ptr(), steps_d.data_ptr(),
         steps_h.ctypes.data_as(ctypes.c_void_p), sp.data_ptr(), E, H, W, int(num_samples),
         mode, int(seed), int(env0), _lib.ptr(draws), _lib.ptr(pos), int(max_keys),
         keys.data_ptr(), n_keys.data_ptr(), present.data_ptr(), inaction.data_ptr(),
-        action.data_ptr(), ws.data_ptr(), int(nbytes.value), _lib.stream_ptr(dev)),
-        "sl_side_effect_densities")
+        action.data_ptr(), ws.data_ptr(), int(nbytes.value), _lib.ptr(ids), kern,
+        _lib.stream_ptr(dev)), "sl_side_effect_densities")
     nk = n_keys.cpu().numpy()
     if (nk > max_keys).any():
         raise ValueError("more than max_keys=%d cell types in a rollout (%d): raise max_keys"
@@ -159,17 +174,34 @@ def earth_mover_distance(a, b, metric="manhattan", wrap_x=True, wrap_y=True, tan
     return emd_cells(a[sel], b[sel], ys, xs, table, extra_mass_penalty)
 
 
+def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
+                       include=None, exclude=None, **rollout_kw):
+    """side_effects.py:95-161 for E finished episodes: one device call for all rollouts
+    (``side_effect_densities``; ``rollout_kw`` goes to it: rng, seed, env_ids, kernel,
+    ...), then the host EMD per episode and key.  Returns a list of
+    {key: [emd, sum(inaction density)]}, one per episode."""
+    init_boards = np.asarray(init_boards) if not hasattr(init_boards, "dim") else init_boards
+    shape = tuple(int(x) for x in init_boards.shape[-2:])
+    zeros = np.zeros(shape)
+    out = []
+    for ina, act in side_effect_densities(init_boards, final_boards, num_steps, spawn_prob,
+                                          num_samples, **rollout_kw):
+        keys = set(ina) | set(act)
+        if include is not None:
+            keys &= set(include)
+        if exclude is not None:
+            keys -= set(exclude)
+        out.append({key: [earth_mover_distance(ina.get(key, zeros), act.get(key, zeros)),
+                          np.sum(ina.get(key, zeros))] for key in keys})
+    return out
+
+
 def side_effect_score(game, num_samples=1000, include=None, exclude=None, **kw):
     """side_effects.py:95-161 for one game-like object (``_init_data['board']``,
     ``board``, ``num_steps``, ``spawn_prob``): {key: [emd, sum(inaction density)]}.
-    The rollout runs on the GPU (``side_effect_densities``); ``kw`` selects its RNG."""
-    (ina, act), = side_effect_densities(game._init_data["board"][None], game.board[None],
-                                        [game.num_steps], game.spawn_prob, num_samples, **kw)
-    keys = set(ina) | set(act)
-    if include is not None:
-        keys &= set(include)
-    if exclude is not None:
-        keys -= set(exclude)
-    zeros = np.zeros(np.shape(game.board))
-    return {key: [earth_mover_distance(ina.get(key, zeros), act.get(key, zeros)),
-                  np.sum(ina.get(key, zeros))] for key in keys}
+    The rollout runs on the GPU (``side_effect_densities``); ``kw`` selects its RNG.
+    The E = 1 case of ``side_effect_scores``."""
+    score, = side_effect_scores(game._init_data["board"][None], game.board[None],
+                                [game.num_steps], game.spawn_prob, num_samples, include,
+                                exclude, **kw)
+    return score
