@@ -369,30 +369,15 @@ typedef struct sl_env_state {
                                  = plane q & 15 of column 2 lane + (q>>4),
                                  rows 32t..32t+31 (sl_bits128.hip).
                                  Derived data, never read unless planes_ok
-                                 bit 1 is set.                                 */
-    int32_t *planes_ok;       /* [B] bit1: goals mirror valid; bit2: goals at
-                                 a fixed point (no spawner, unchanged by the
-                                 last step: the rule is skipped); bit3: the
-                                 board's draw planes (elig_planes) hold its
-                                 eligible cells as the last step left them;
-                                 bit4 (128x128): the mirror holds all six goal
-                                 planes (spawn_flags bit3), not only colours;
-                                 bit5 (128x128): the goals are the pool level's,
-                                 as reset (set by the reset, cleared by the first
-                                 change): their colours come from the pool's
-                                 goal_planes; bit6 (128x128): board_planes hold
-                                 the board; bit7: with bit6, the uint16 board
-                                 is complete too (else only its band-edge rows);
-                                 bit8: with bit6, the board's planes 12-14 are
-                                 zero and not kept.
-                                 Anything
-                                 that writes the goals other than the 64x64
-                                 kernel and its reset clears it.               */
+                                 has SL_POK_GOALS_MIRROR.                      */
+    int32_t *planes_ok;       /* [B] which of the derived copies above and below
+                                 are valid: SL_POK_* bits (sl_planes_ok_bits,
+                                 after this struct).  Zero-init.               */
     uint32_t *elig_planes;    /* replay mode, 128x128, [B][1024] words: the
                                  draw planes [tensor][band t][word w][lane] (bit
                                  y of word w of lane j = cell (32t + y, 2j + w)).
                                  The step kernel leaves the advanced board's
-                                 eligible cells in tensor 0's (planes_ok bit 3);
+                                 eligible cells in tensor 0's (SL_POK_ELIG);
                                  the next step's count patches the rows its
                                  action edited and counts them; the draw pass
                                  replaces each drawing tensor's eligible cells
@@ -407,23 +392,23 @@ typedef struct sl_env_state {
                                  draw planes; no obs_out, or packed views of at
                                  most 96 rows, which it writes from the planes;
                                  sl_env_cfg.board_mode SL_BOARD_AUTO -- keeps
-                                 the board here (planes_ok bit6) and writes of
+                                 the board here (SL_POK_BOARD_PLANES) and writes of
                                  the uint16 board only its band-edge rows (32t,
                                  32t + 31) and the cells the action and exits
-                                 edit: bit7 then says the uint16 board is
-                                 complete.  sl_env_board_sync completes it (a
+                                 edit: SL_POK_BOARD_FULL then says the uint16
+                                 board is complete.  sl_env_board_sync completes it (a
                                  per-env no-op for envs not in planes or
                                  already complete); the library's other entry
                                  points that read or write st->board do so
                                  themselves.  A caller that writes the uint16
-                                 board clears planes_ok (as for the goals
-                                 mirror).  64x64: board_planes == planes puts
+                                 board: see sl_planes_ok_bits.
+                                 64x64: board_planes == planes puts
                                  the board's planes in half 0 of the goals
                                  mirror (Philox steps without capture: with no
                                  obs_out, with packed views, or with channel
                                  views of at most 64x64 and 1094 cells into a
                                  16-byte aligned obs_out, all written from the
-                                 planes; bit 7 only after a sync).             */
+                                 planes; SL_POK_BOARD_FULL only after a sync). */
     uint32_t board_zero;      /* plane mode (64x64, 128x128): cell bits (planes) that are
                                  0 in every board of the batch and that no rule,
                                  action or reset can set (the caller's promise:
@@ -431,8 +416,8 @@ typedef struct sl_env_state {
                                  LIFE / COLOR_R, not toggled powers / colours);
                                  their planes are neither loaded nor stored.
                                  To widen it, complete the board first
-                                 (sl_env_board_sync) and clear planes_ok bits
-                                 6-7.  0 = every plane.                        */
+                                 (sl_env_board_sync) and clear SL_POK_BOARD.
+                                 0 = every plane.                              */
     int32_t planes_live;      /* host flag, kept by the library: a plane-mode
                                  step set it (some board may be in planes);
                                  a demotion clears it.  While 0 the syncs the
@@ -440,6 +425,59 @@ typedef struct sl_env_state {
                                  caller stepping a slice (a copy of this
                                  struct) ORs the slice's flag back in.         */
 } sl_env_state;
+
+/*
+ * The bits of sl_env_state.planes_ok[b]: which derived copies of env b's state are
+ * valid.  "Step" is a step of the bit-sliced 64x64 / 128x128 kernels; the per-cell
+ * kernels (sl_env_action and sl_env_advance, and sl_env_step on other shapes or with
+ * SL_KERNEL_GENERIC) keep no copies and store 0.  Every reset rewrites the word (it
+ * writes the uint16 board and goals): 64x64 to SL_POK_GOALS_MIRROR (it rebuilds the
+ * mirror), 128x128 to SL_POK_GOALS_LEVEL.
+ *
+ * SL_POK_GOALS_MIRROR  64x64, 128x128.  `planes` mirrors the goals.  Set by the 64x64
+ *     reset and by a step that advanced the goals (it rebuilds a stale mirror).
+ * SL_POK_GOALS_FIXED   64x64, 128x128.  The goals hold no spawner and came through a
+ *     step unchanged: the rule is skipped from then on.  Set by that step.
+ * SL_POK_GOALS_SIX     128x128.  The mirror holds all six goal planes (spawn_flags
+ *     bits 1 and 3 clear), not only the colours.  Set by the step that (re)built it.
+ * SL_POK_GOALS_LEVEL   128x128.  The goals are still the pool level's: their colours
+ *     come from the pool's goal_planes.  Set by the reset, cleared by the first step
+ *     that changes the goals.
+ * SL_POK_ELIG          128x128 replay with elig_planes.  The board's draw planes hold
+ *     its eligible cells as the last step left them.  Set by a decided replay step,
+ *     cleared by every other step.
+ * SL_POK_BOARD_PLANES  64x64, 128x128.  board_planes hold the board.  Set by a
+ *     plane-mode step; cleared (after completing the uint16 board) by every library
+ *     entry point that writes it: a step in another mode, sl_env_action,
+ *     sl_env_advance.
+ * SL_POK_BOARD_FULL    64x64, 128x128; with SL_POK_BOARD_PLANES.  The uint16 board is
+ *     complete too (else only its band-edge rows and exit cells).  Set by
+ *     sl_env_board_sync and by a 128x128 step into plane mode, cleared by the next
+ *     plane-mode step.
+ * SL_POK_BOARD_LO12    128x128 decided replay; with SL_POK_BOARD_PLANES.  Board planes
+ *     12-14 are zero and not kept.  Set by the step into plane mode that found them
+ *     zero.
+ *
+ * A caller that writes state from outside the library:
+ *   - the goals: clear SL_POK_GOALS;
+ *   - the uint16 board: complete it first (sl_env_board_sync), write, then clear
+ *     SL_POK_ELIG | SL_POK_BOARD (and widen board_zero first if the cells written use
+ *     planes in it: see there);
+ *   - everything (a restored checkpoint): store 0.
+ */
+enum sl_planes_ok_bits {
+    SL_POK_GOALS_MIRROR = 2,
+    SL_POK_GOALS_FIXED = 4,
+    SL_POK_ELIG = 8,
+    SL_POK_GOALS_SIX = 16,
+    SL_POK_GOALS_LEVEL = 32,
+    SL_POK_BOARD_PLANES = 64,
+    SL_POK_BOARD_FULL = 128,
+    SL_POK_BOARD_LO12 = 256,
+    SL_POK_GOALS = SL_POK_GOALS_MIRROR | SL_POK_GOALS_FIXED | SL_POK_GOALS_SIX |
+                   SL_POK_GOALS_LEVEL,
+    SL_POK_BOARD = SL_POK_BOARD_PLANES | SL_POK_BOARD_FULL | SL_POK_BOARD_LO12
+};
 
 /* A device-resident level pool (the level_iterator's levels). */
 typedef struct sl_level_pool {
@@ -593,7 +631,7 @@ int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const int32_t *acti
                 void *stream);
 
 /* Complete the uint16 board of every env whose board lives in st->board_planes
- * (planes_ok bit6 without bit7): needed before reading st->board directly after
+ * (SL_POK_BOARD_PLANES without SL_POK_BOARD_FULL): needed before reading st->board directly after
  * steps that kept the board in planes.  No-op without board_planes. */
 int sl_env_board_sync(sl_env_state *st, void *stream);
 

@@ -601,6 +601,8 @@ enum : int {
     R_PX = 32,           // prior_x[16]
     R_PY = 48            // prior_y[16]
 };
+// R_POK of goals a step skips: mirrored and at their fixed point
+constexpr int kPokGoalsSkip = SL_POK_GOALS_MIRROR | SL_POK_GOALS_FIXED;
 
 __device__ __forceinline__ u32 load_record(const sl_env_state &st, const int32_t *actions,
                                            int64_t b, int lane) {

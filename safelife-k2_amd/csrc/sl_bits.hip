@@ -262,7 +262,7 @@ __device__ __forceinline__ void wave_reset(const sl_env_state &st, const sl_leve
         }
     }
     if (lane == 0) {
-        if (mg) st.planes_ok[b] = 2;   // after reset_scalars cleared it
+        if (mg) st.planes_ok[b] = SL_POK_GOALS_MIRROR;   // after reset_scalars cleared it
         st.exit_count[b] = n_exit;
         for (int e = n_exit; e < SL_MAX_EXITS; e++) {
             st.exit_y[b * SL_MAX_EXITS + e] = 0;
@@ -506,8 +506,9 @@ __device__ __forceinline__ void issue_pre(const sl_env_state &st, const int32_t 
 }
 
 // The goals' step of the two 64x64 kernels, for goals not at their fixed point (the
-// callers skip those: (pok & 6) == 6).  The goals come from their bit-plane mirror mg
-// when it is valid (pok bit 1; mg may be null: no mirror), else from the cells gg,
+// callers skip those: (pok & kPokGoalsSkip) == kPokGoalsSkip).  The goals come from their
+// bit-plane mirror mg when it is valid (pok has SL_POK_GOALS_MIRROR; mg may be null: no
+// mirror), else from the cells gg,
 // transposed; after the rule the mirror takes the words whose 32 cells changed (all of
 // them if rebuilt), gcol the new colour planes and gg the changed rows.  Returns the
 // goals' planes_ok bits after the step (pok without a mirror); the caller stores them.
@@ -518,7 +519,7 @@ __device__ __forceinline__ int goals_step64(u32 *gg, u32 *mg, int pok, int lane,
                                             int64_t pos_g, u32 gcol[3][2]) {
     int ok = pok;
     u32 PG[32];
-    if (pok & 2) {
+    if (pok & SL_POK_GOALS_MIRROR) {
 #pragma unroll
         for (int q = 0; q < 32; q++) PG[q] = mg[q * 64];    // goal planes
     } else {
@@ -529,14 +530,14 @@ __device__ __forceinline__ int goals_step64(u32 *gg, u32 *mg, int pok, int lane,
     rule_planes<PIN>(PG, cg, Geo64<MODE>{lane, ssrc, pos_g, 0}, sc, 1u);
     const u32 rg = wave_or(cg[0] | cg[1]);
     if (mg) {
-        const bool all = !(pok & 2);
+        const bool all = !(pok & SL_POK_GOALS_MIRROR);
 #pragma unroll
         for (int w = 0; w < 2; w++)
             if (all || cg[w])
 #pragma unroll
                 for (int k = 0; k < 16; k++) mg[(k + 16 * w) * 64] = PL(PG, k, w);
         const bool fixed = rg == 0 && __ballot((PL(PG, 7, 0) | PL(PG, 7, 1)) != 0u) == 0ull;
-        ok = 2 | (fixed ? 4 : 0);
+        ok = SL_POK_GOALS_MIRROR | (fixed ? SL_POK_GOALS_FIXED : 0);
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -577,7 +578,7 @@ __device__ __forceinline__ void step_env(const sl_env_state &st, const StepArgs 
     const u32 V = pre.V;
     // goals: a goals board without spawners that came through a step unchanged is at
     // a fixed point of the (then deterministic) rule and never changes again
-    // (planes_ok bit 2); such envs read only the three colour planes of the mirror,
+    // (SL_POK_GOALS_FIXED); such envs read only the three colour planes of the mirror,
     // which are speculatively in flight before the record says which case holds
     u32 gcol[3][2];                    // goal colour planes, kept for the scores
 #pragma unroll
@@ -585,14 +586,14 @@ __device__ __forceinline__ void step_env(const sl_env_state &st, const StepArgs 
         gcol[k][0] = pre.g[k][0];
         gcol[k][1] = pre.g[k][1];
     }
-    const int pok = (mg && st.planes_ok) ? rec(V, R_POK) & 6 : 0;
+    const int pok = (mg && st.planes_ok) ? rec(V, R_POK) & kPokGoalsSkip : 0;
 
     const SpawnCtx sc = spawn_ctx(a, b, rec(V, R_SPAWN));
     int64_t pos_b, pos_g;
     const StreamSrc ssrc = stream_src<MODE>(a, fx.scratch, st.B, b, pos_b, pos_g);
 
     // ---- goals
-    if ((pok & 6) != 6) {
+    if ((pok & kPokGoalsSkip) != kPokGoalsSkip) {
         const int ok = goals_step64<false, MODE>(gg, mg, pok, lane, sc, ssrc, pos_g, gcol);
         if (ok != pok && lane == 0) st.planes_ok[b] = ok;
     }
@@ -778,10 +779,10 @@ k_env_step_bits64(StepKArgs ka) {
 // stores only the words that changed; no transposes.  Planes in
 // sl_env_state.board_zero (all zero in every board of the batch, for good: the C3 / C4
 // pools never use cell bits 7 and 11-14) are neither loaded nor stored, and the kept
-// ones are packed (PlaneSlots): 6 of the 8 KiB are read.  planes_ok bit 6: the planes hold the board; bit 7: so does the uint16
-// board (a sync, or a reset, wrote it), which a plane step otherwise leaves stale
-// (exits aside: the epilogue writes them in both).
-constexpr int kPok64Board = 64, kPok64Full = 128;
+// ones are packed (PlaneSlots): 6 of the 8 KiB are read.  SL_POK_BOARD_PLANES: the
+// planes hold the board; SL_POK_BOARD_FULL: so does the uint16 board (a sync wrote it),
+// which a plane step otherwise leaves stale (exits aside: the epilogue writes them in
+// both).
 
 // The planes outside `zero` packed word after word: word q (plane q & 15 of column
 // word q >> 4) at position pos(q), the number of kept words below it, so the kept words
@@ -899,8 +900,8 @@ __global__ void __launch_bounds__(64) k_board_sync64(sl_env_state st, int demote
     const int64_t b = blockIdx.x;
     const int lane = threadIdx.x;
     const int pok = __builtin_amdgcn_readfirstlane(st.planes_ok[b]);
-    if (!(pok & kPok64Board)) return;
-    if (!(pok & kPok64Full)) {
+    if (!(pok & SL_POK_BOARD_PLANES)) return;
+    if (!(pok & SL_POK_BOARD_FULL)) {
         const PlaneSlots<0> ps = PlaneSlots<0>::of(st.board_zero);
         const u32 *bp = st.planes + b * 4096 + lane;
         u32 P[32];
@@ -913,7 +914,8 @@ __global__ void __launch_bounds__(64) k_board_sync64(sl_env_state st, int demote
         for (int y = 0; y < 32; y++) gb[y * 32] = P[y];
     }
     if (lane == 0)
-        st.planes_ok[b] = demote ? pok & ~(kPok64Board | kPok64Full) : pok | kPok64Full;
+        st.planes_ok[b] = demote ? pok & ~(SL_POK_BOARD_PLANES | SL_POK_BOARD_FULL)
+                                 : pok | SL_POK_BOARD_FULL;
 }
 
 // Replay-mode count of env b (SL_RNG_STREAM), one wave, after k_env_action (one lane
@@ -946,11 +948,11 @@ k_stream_prologue64(StepKArgs ka) {
         rule_planes(P, ch, gbd, sc, 0u);
         nb = wave_total(gbd.count);
     }
-    // goals at their fixed point (planes_ok bit 2) hold no spawner: no draws
-    const int pok = (st.planes && st.planes_ok) ? rec(V, R_POK) & 6 : 0;
+    // goals at their fixed point (SL_POK_GOALS_FIXED) hold no spawner: no draws
+    const int pok = (st.planes && st.planes_ok) ? rec(V, R_POK) & kPokGoalsSkip : 0;
     int ng = 0;
-    if ((pok & 6) != 6 && (spf & 2)) {
-        if (pok & 2) {
+    if ((pok & kPokGoalsSkip) != kPokGoalsSkip && (spf & 2)) {
+        if (pok & SL_POK_GOALS_MIRROR) {
             const u32 *mg = st.planes + b * 4096 + 2048 + lane;
 #pragma unroll
             for (int q = 0; q < 32; q++) P[q] = mg[q * 64];

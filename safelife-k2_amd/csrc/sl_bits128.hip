@@ -22,7 +22,7 @@
 //    the board's changed rows and the goals' changed 64-byte row sectors are stored;
 //  * goals: a bit-plane mirror (sl_env_state.planes, [B][band][32 words][64 lanes])
 //    holds their planes.  Goals without spawners that came through a step unchanged
-//    are at a fixed point of the rule (planes_ok bit 2): the rule is skipped and only
+//    are at a fixed point of the rule (SL_POK_GOALS_FIXED): the rule is skipped and only
 //    their three colour planes are read, per band, for the scores;
 //  * the action (execute_action / move_agent, safelife_game.py:308-393) has run
 //    before this kernel: k_env_action (one lane per env, both RNG modes) leaves the
@@ -466,8 +466,8 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
     __attribute__((address_space(3))) u32 *spool = (__attribute__((address_space(3))) u32 *)spool_;
     __shared__ uint16_t slots_[kDrawSlots];
     lds_u16 *slots = (lds_u16 *)slots_;
-    const int pok_all = rec(V, R_POK), pok = pok_all & 6;
-    int gok = pok_all & (6 | 16 | 32);   // the goals' planes_ok bits after this step
+    const int pok_all = rec(V, R_POK), pok = pok_all & kPokGoalsSkip;
+    int gok = pok_all & SL_POK_GOALS;   // the goals' planes_ok bits after this step
     const Scratch w = scratch_of(fx.scratch, st.B);
     // replay with draw planes: the spawns come decided from them (k_stream_draw128), for
     // the tensors that draw (scratch act[B + b] bit 0 board, bit 1 goals), and the
@@ -487,13 +487,14 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
     // their colour planes (all words rewritten when it was stale, else the changed
     // ones).  Goals whose cells use only planes 0, 3, 4 and 9-11 and hold no spawner
     // (spawn_flags bits 1 and 3 clear: the rule then creates no other bit) keep those
-    // six planes there (planes_ok bit 4) and are read back from them -- 12 of the
+    // six planes there (SL_POK_GOALS_SIX) and are read back from them -- 12 of the
     // 32 KiB of their cells, no transposes -- with the halo rows from the cells
     const int spf = rec(V, R_SPF);
-    if ((pok & 6) != 6) {
-        const bool all = !(pok & 2);
+    if ((pok & kPokGoalsSkip) != kPokGoalsSkip) {
+        const bool all = !(pok & SL_POK_GOALS_MIRROR);
         const bool gplanes = (spf & (2 | 8)) == 0;
-        const bool from_mirror = gplanes && (pok_all & 16) && (pok & 2);
+        const bool from_mirror = gplanes && (pok_all & SL_POK_GOALS_SIX) &&
+                                 (pok & SL_POK_GOALS_MIRROR);
         u32 changed = 0, spawners = 0;
         u32 up = gg[(N - 1) * RS], row0 = from_mirror ? gg[0] : 0u;
 #pragma unroll 1
@@ -550,7 +551,8 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
             }
         }
         const bool fixed = changed == 0 && __ballot(spawners != 0u) == 0ull;
-        gok = 2 | (fixed ? 4 : 0) | (gplanes ? 16 : 0) | (changed == 0 ? pok_all & 32 : 0);
+        gok = SL_POK_GOALS_MIRROR | (fixed ? SL_POK_GOALS_FIXED : 0) |
+              (gplanes ? SL_POK_GOALS_SIX : 0) | (changed == 0 ? pok_all & SL_POK_GOALS_LEVEL : 0);
         wait_vm();          // the mirror words are read back below
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -567,22 +569,22 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
                     (int64_t)(roll >= 0 ? rec(V, R_LI) : 0) * (16 * NB * N);
     const int sdy = roll < 0 ? 0 : roll >> 16, sdx = roll < 0 ? 0 : roll & 0xFFFF;
     const bool start_hi = (rec(V, R_SPF) & 4) != 0;     // start board may use bits 12-14
-    // goals still the level's (planes_ok bit 5, after this step's goals): their colour
+    // goals still the level's (SL_POK_GOALS_LEVEL, after this step's goals): their colour
     // planes from the pool (cache-resident) instead of the mirror (HBM)
-    const u32 *gp = (roll >= 0 && (gok & 32) && pool.goal_planes)
+    const u32 *gp = (roll >= 0 && (gok & SL_POK_GOALS_LEVEL) && pool.goal_planes)
                         ? pool.goal_planes + (int64_t)rec(V, R_LI) * (3 * NB * N) : nullptr;
     int pts = 0, scr = 0, pos = 0, side = 0;
     // plane mode (fx.plane_mode, Philox only): the board lives in st.board_planes, in
-    // the mirror's layout; pin = this env's planes hold it (planes_ok bit 6; else this
+    // the mirror's layout; pin = this env's planes hold it (SL_POK_BOARD_PLANES; else this
     // step reads the uint16 board and writes every plane word).  Of the uint16 board
     // only the band-edge rows 32t and 32t + 31 are kept, for the halos
     const bool pmode = (MODE == SPAWN_PHILOX || MODE == SPAWN_DECIDED) && fx.plane_mode;
-    const bool pin = pmode && (pok_all & 64);
-    // planes_ok bit 8: the board's planes 12-14 are zero (no cell type uses those bits;
+    const bool pin = pmode && (pok_all & SL_POK_BOARD_PLANES);
+    // SL_POK_BOARD_LO12: the board's planes 12-14 are zero (no cell type uses those bits;
     // the rule and the actions never set them), so they are neither loaded nor stored.
     // Decided replay only: in the Philox form the selects cost more than the 6 KiB they
     // save (70.2 vs 72.9 M env-steps/s, +4 % for replay; profiles/r05am_ab_zero_planes.txt)
-    const bool lo12 = MODE == SPAWN_DECIDED && pin && (pok_all & 256);
+    const bool lo12 = MODE == SPAWN_DECIDED && pin && (pok_all & SL_POK_BOARD_LO12);
     u32 hi12 = 0u;              // a step into plane mode: any of them set
     const LanePtr<u32> bpl{pmode ? st.board_planes + b * (int64_t)(NB * MW) : nullptr};
     // ... and the cells round the agent the next step's action reads
@@ -815,13 +817,15 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
     const int points = VIEW ? pts : wave_total(pts), score = VIEW ? scr : wave_total(scr);
     const int possible = VIEW ? pos : wave_total(pos);
     const int side_total = VIEW ? side : wave_total(side);
-    // goals mirror bits, and bit 3 = the board's draw planes hold the advanced board's
-    // eligible cells (decided replay only: any other step clears it)
-    // bit 6: the planes hold the board; bit 7: so does the whole uint16 board (a step
-    // into plane mode stored its changed rows as well)
+    // goals mirror bits, and SL_POK_ELIG = the board's draw planes hold the advanced
+    // board's eligible cells (decided replay only: any other step clears it)
+    // SL_POK_BOARD_PLANES: the planes hold the board; SL_POK_BOARD_FULL: so does the whole
+    // uint16 board (a step into plane mode stored its changed rows as well)
     const bool z12 = MODE == SPAWN_DECIDED && (pin ? lo12 : __ballot(hi12 != 0u) == 0ull);
-    const int ok = gok | (me.base ? 8 : 0) |
-                   (pmode ? (pin ? 64 : 64 | 128) | (z12 ? 256 : 0) : 0);
+    const int ok = gok | (me.base ? SL_POK_ELIG : 0) |
+                   (pmode ? (pin ? SL_POK_BOARD_PLANES : SL_POK_BOARD_PLANES | SL_POK_BOARD_FULL) |
+                                (z12 ? SL_POK_BOARD_LO12 : 0)
+                          : 0);
     if (ok != pok_all && lane_now() == 0) st.planes_ok[b] = ok;
     // the epilogue's inputs, loaded now (in flight with the row stores) rather than held
     // through the bands: the reward, the bonus term and the record again (L2)
@@ -880,8 +884,8 @@ void launch_step128(const Step128KArgs &ka, bool view, hipStream_t s) {
 // act[] -- so the board read here is the acted-on one: the eligible cells of the board
 // and of the goals, band by band (scratch counts[2b], [2b+1]; sl_exclusive_scan_i64
 // turns them into each tensor's first uniform).  The work of k_env_count (sl_env.hip)
-// on the bit-sliced rule.  When the last step was a decided replay step (planes_ok
-// bit 3) the board's eligible cells are already in its draw planes, bar the rows the
+// on the bit-sliced rule.  When the last step was a decided replay step (SL_POK_ELIG)
+// the board's eligible cells are already in its draw planes, bar the rows the
 // action edited: 2 KiB per env and a few board rows instead of the 32 KiB board.
 __device__ __forceinline__ void count_env128(const Step128KArgs &ka, int64_t b, int lane,
                                             int &nb_out, int &ng_out, int &dfl_out) {
@@ -905,11 +909,12 @@ __device__ __forceinline__ void count_env128(const Step128KArgs &ka, int64_t b, 
     const StreamSrc none{nullptr, 0, nullptr};
     // the draw planes: each counted tensor's eligible cells, for k_stream_draw128
     u32 *dp = st.elig_planes ? st.elig_planes + b * kEligStride + kDrawPlanes + lane : nullptr;
-    // plane mode (sl_env_state.board_planes, planes_ok bit 6): the board is read from
+    // plane mode (sl_env_state.board_planes, SL_POK_BOARD_PLANES): the board is read from
     // its planes -- only the four eligibility planes -- after the action's edits
     // (k_env_action_planes128 wrote the uint16 cells, listed in act[3B + b]) have been
     // put into them here, for this count and for the step kernel
-    const bool pm = ka.fx.plane_mode && st.board_planes && (rec(V, R_POK) & 64);
+    const bool pm = ka.fx.plane_mode && st.board_planes &&
+                    (rec(V, R_POK) & SL_POK_BOARD_PLANES);
     u32 *const bpw = pm ? st.board_planes + b * (int64_t)(NB * MW) : nullptr;
     const u32 zero = st.board_zero;          // planes no board holds (never stored)
     auto pload = [&](int t, int k) -> u32 {  // (past the vector L1: the edits just stored)
@@ -1071,9 +1076,9 @@ __device__ __forceinline__ void count_env128(const Step128KArgs &ka, int64_t b, 
         return n0 + wave_total(dn);
     };
     // a board or goals without spawners (spawn_flags, set at reset: no rule or action
-    // creates one) draws nothing; nor do goals at their fixed point (planes_ok bit 2)
+    // creates one) draws nothing; nor do goals at their fixed point (SL_POK_GOALS_FIXED)
     const int spf = rec(V, R_SPF) | (ka.ctp ? 1 : 0);     // toggling powers can make one
-    const bool next = st.elig_planes && (rec(V, R_POK) & 8);
+    const bool next = st.elig_planes && (rec(V, R_POK) & SL_POK_ELIG);
     int nb = 0;
     bool put = false;
     if (spf & 1) {
@@ -1086,7 +1091,8 @@ __device__ __forceinline__ void count_env128(const Step128KArgs &ka, int64_t b, 
         }
     }
     if (!put) put_edits();
-    const int ng = ((rec(V, R_POK) & 6) == 6 || !(spf & 2)) ? 0 : count(gg, 1);
+    const int ng = ((rec(V, R_POK) & kPokGoalsSkip) == kPokGoalsSkip || !(spf & 2))
+                       ? 0 : count(gg, 1);
     const int dfl = (nb ? 1 : 0) | (ng ? 2 : 0);
     if (lane == 0) {
         w.counts[2 * b] = nb;
@@ -1362,7 +1368,7 @@ k_stream_draw128_bits(Step128KArgs ka) {
 
 // ---- board planes (sl_env_state.board_planes, plane mode)
 // k_env_action for a plane-mode step (one lane per env): an env whose board is in
-// planes (planes_ok bit 6) reads the cells its action can touch from the uint16 board
+// planes (SL_POK_BOARD_PLANES) reads the cells its action can touch from the uint16 board
 // -- the step kernel keeps them current (the agent's row, and its column two rows up
 // and down) -- and writes its edits there.  Other envs take the uint16 action
 // (env_action_one); an env with no scratch row list entry is then not in plane mode.
@@ -1371,7 +1377,7 @@ k_env_action_planes128(sl_env_state st, const int32_t *__restrict__ actions, int
                        int64_t *__restrict__ act) {
     const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (b >= st.B) return;
-    if (!(st.planes_ok[b] & 64)) {
+    if (!(st.planes_ok[b] & SL_POK_BOARD_PLANES)) {
         env_action_one<false>(st, actions, ctp, ctc, act, b);
         return;
     }
@@ -1425,8 +1431,8 @@ __global__ void __launch_bounds__(64) k_board_sync128(sl_env_state st, int demot
     const int64_t b = blockIdx.x;
     const int lane = threadIdx.x;
     const int pok = __builtin_amdgcn_readfirstlane(st.planes_ok[b]);
-    if (!(pok & 64)) return;
-    if (!(pok & 128)) {
+    if (!(pok & SL_POK_BOARD_PLANES)) return;
+    if (!(pok & SL_POK_BOARD_FULL)) {
         // the exit cells hold their colour in the uint16 board only (the epilogue
         // writes them): read before the rows are rewritten, put back after
         uint16_t *cells = st.board + b * (int64_t)(N * N);
@@ -1453,7 +1459,7 @@ __global__ void __launch_bounds__(64) k_board_sync128(sl_env_state st, int demot
         wait_vm();
         if (ei >= 0) cells[ei] = ev;
     }
-    if (lane == 0) st.planes_ok[b] = demote ? pok & ~(64 | 128 | 256) : pok | 128;
+    if (lane == 0) st.planes_ok[b] = demote ? pok & ~SL_POK_BOARD : pok | SL_POK_BOARD_FULL;
 }
 
 }  // namespace

@@ -266,7 +266,7 @@ k_env_advance(sl_env_state st, StepArgs a, const int64_t *__restrict__ offsets,
     }
     if (threadIdx.x == 0) {
         st.num_steps[b] += 1;
-        if (st.planes_ok) st.planes_ok[b] = 0;
+        if (st.planes_ok) st.planes_ok[b] = 0;      // (the per-cell path keeps no SL_POK_* copy)
     }
 }
 
@@ -966,6 +966,17 @@ static int demote_planes(sl_env_state *st, hipStream_t s) {
     return rc;
 }
 
+// replay draws from the device generator's ring (sl_env_cfg.mt) instead of cfg->draws
+static void draws_from_ring(StepArgs &a, const sl_mt19937 &mt) {
+    a.draws = mt.ring;
+    a.n_draws = INT64_MAX;
+    a.draw_mask = mt.ring_draws - 1;
+    if (mt.bit_ring) {
+        a.draw_bits = reinterpret_cast<const uint32_t *>(mt.ring);
+        a.bits_thr = mt.bits_thr;
+    }
+}
+
 extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const int32_t *actions,
                            const sl_env_cfg *cfg, double *reward, uint8_t *done,
                            uint8_t *info_flags, int32_t *ep_len, int32_t *ep_reward,
@@ -997,15 +1008,7 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
 
     if (cfg->rng_mode != SL_RNG_STREAM && cfg->rng_mode != SL_RNG_PHILOX) return SL_EINVAL;
     const bool replay = cfg->rng_mode == SL_RNG_STREAM;
-    if (replay && cfg->mt) {       // draws from the device generator's ring
-        a.draws = cfg->mt->ring;
-        a.n_draws = INT64_MAX;
-        a.draw_mask = cfg->mt->ring_draws - 1;
-        if (cfg->mt->bit_ring) {
-            a.draw_bits = reinterpret_cast<const uint32_t *>(cfg->mt->ring);
-            a.bits_thr = cfg->mt->bits_thr;
-        }
-    }
+    if (replay && cfg->mt) draws_from_ring(a, *cfg->mt);
     if (replay && (!cfg->stream_pos || (!a.draws && a.n_draws > 0))) return SL_EINVAL;
     if (cfg->stream_phase < 0 || cfg->stream_phase > 2 || (cfg->stream_phase && !replay) ||
         (cfg->stream_phase == 2 && !cfg->stream_base))
@@ -1275,15 +1278,7 @@ extern "C" int sl_env_advance(sl_env_state *st, const sl_env_cfg *cfg, void *str
     a.env0 = cfg->env0;
     a.draws = cfg->draws;
     a.n_draws = cfg->n_draws;
-    if (replay && cfg->mt) {
-        a.draws = cfg->mt->ring;
-        a.n_draws = INT64_MAX;
-        a.draw_mask = cfg->mt->ring_draws - 1;
-        if (cfg->mt->bit_ring) {
-            a.draw_bits = reinterpret_cast<const uint32_t *>(cfg->mt->ring);
-            a.bits_thr = cfg->mt->bits_thr;
-        }
-    }
+    if (replay && cfg->mt) draws_from_ring(a, *cfg->mt);
     if (replay) {
         if (!set_lds((const void *)k_env_count, lds)) return SL_ETOOBIG;
         hipLaunchKernelGGL(k_env_count, dim3((unsigned)B), dim3(NT), lds, s, *st, sc.counts);

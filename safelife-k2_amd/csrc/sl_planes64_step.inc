@@ -30,14 +30,14 @@
     u32 *bp = st.planes + b * 4096 + lane;
     const u32 V = pre.V;
     const int pok_all = rec(V, R_POK);
-    const bool pin = (pok_all & kPok64Board) != 0;
+    const bool pin = (pok_all & SL_POK_BOARD_PLANES) != 0;
     u32 gcol[3][2];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         gcol[k][0] = pre.g[k][0];
         gcol[k][1] = pre.g[k][1];
     }
-    const int pok = pok_all & 6;
+    const int pok = pok_all & kPokGoalsSkip;
 
     const SpawnCtx sc = spawn_ctx(a, b, rec(V, R_SPAWN));
     const StreamSrc ssrc{a.draws, a.n_draws, nullptr, a.draw_mask, a.draw_bits};
@@ -45,7 +45,7 @@
     // ---- goals: the mirror is half 1 of the planes; their planes_ok bits after this
     // step go out with the board's below
     int gok = pok;
-    if ((pok & 6) != 6)
+    if ((pok & kPokGoalsSkip) != kPokGoalsSkip)
         gok = goals_step64<true, SPAWN_PHILOX>(gg, mg, pok, lane, sc, ssrc, 0, gcol);
     __builtin_amdgcn_sched_barrier(0);
 
@@ -175,7 +175,7 @@
             }
         }
     }
-    const int ok = gok | kPok64Board;
+    const int ok = gok | SL_POK_BOARD_PLANES;
     if (ok != pok_all && lane == 0) st.planes_ok[b] = ok;
     if (OBS) {
         const bool rw = kernarg().fx.obs_rw != 0;

@@ -21,6 +21,11 @@ SL_MAX_EXITS = 8
 SL_BONUS_PERIOD_MAX = 16
 SL_OBS_NONE, SL_OBS_PACKED, SL_OBS_CHANNELS, SL_OBS_CHANNELS_U8 = 0, 1, 2, 3
 SL_OBS_CHANNELS_F32, SL_OBS_CHANNELS_BF16 = 4, 5
+# sl_env_state.planes_ok bits (enum sl_planes_ok_bits; tests/test_capi.py compares)
+SL_POK_GOALS_MIRROR, SL_POK_GOALS_FIXED, SL_POK_ELIG, SL_POK_GOALS_SIX = 2, 4, 8, 16
+SL_POK_GOALS_LEVEL, SL_POK_BOARD_PLANES, SL_POK_BOARD_FULL, SL_POK_BOARD_LO12 = 32, 64, 128, 256
+SL_POK_GOALS = SL_POK_GOALS_MIRROR | SL_POK_GOALS_FIXED | SL_POK_GOALS_SIX | SL_POK_GOALS_LEVEL
+SL_POK_BOARD = SL_POK_BOARD_PLANES | SL_POK_BOARD_FULL | SL_POK_BOARD_LO12
 
 _ERRORS = {SL_EINVAL: "invalid argument / shape", SL_EHIP: "HIP launch error",
            SL_ETOOBIG: "board too large for this kernel"}

@@ -129,14 +129,7 @@ class SafeLifeGame:
 
     @board.setter
     def board(self, value):
-        v = self._upload(value)
-        self._venv._allow_board_bits(self._venv._device_board_bits(v))
-        self._venv.board[self._idx].copy_(v)
-        self._set("spawn_flags", self._st("spawn_flags") | 1)   # may now hold a spawner
-        self._venv._may_spawn = True
-        # bit 3: the board's draw planes (128x128 replay) described the old board;
-        # bits 6-7: the board's bit planes (sl_env_state.board_planes) are stale
-        self._venv.planes_ok[self._idx].bitwise_and_(~(8 | 64 | 128))
+        self._venv.write_board(self._idx, value)
         self.rescore()
 
     @property
@@ -145,18 +138,8 @@ class SafeLifeGame:
 
     @goals.setter
     def goals(self, value):
-        self._venv.goals[self._idx].copy_(self._upload(value))
-        self._set("spawn_flags", self._st("spawn_flags") | 2)
-        self._venv._may_spawn = True
-        self._venv.planes_ok[self._idx].zero_()        # the goals mirror is stale
+        self._venv.write_goals(self._idx, value)
         self.rescore()
-
-    def _upload(self, a):
-        torch = self._venv.torch
-        a = np.ascontiguousarray(a, dtype=np.uint16)
-        if a.shape != (self.height, self.width):
-            raise ValueError("board must be %dx%d" % (self.height, self.width))
-        return torch.from_numpy(a).to(self._venv.device)
 
     @property
     def agent_loc(self):
@@ -276,7 +259,7 @@ class SafeLifeGame:
         if goals is not None:
             # current_points(goals=...) scores the board against other goals; the
             # env's stored terms are left alone
-            g = self._upload(goals)
+            g = self._venv._cells(goals)
             tmp = self._venv.torch.zeros(2, dtype=self._venv.torch.int32, device=self._venv.device)
             s.goals = g.data_ptr()
             s.score, s.possible = tmp.data_ptr(), tmp.data_ptr() + 4
@@ -411,7 +394,9 @@ class SafeLifeGame:
     def serialize(self):
         """safelife_game.py:184-194 + GameWithGoals.serialize (:571-574)."""
         return {"spawn_prob": self.spawn_prob, "orientation": self.orientation,
-                "agent_loc": tuple(int(x) for x in self.agent_loc), "board": self.board,
+                "agent_loc": tuple(int(x) for x in self.agent_loc),
+                # (not through `board`: a snapshot is no per-step reader, board_mode="auto")
+                "board": self._venv._synced_board()[self._idx].cpu().numpy(),
                 "class": GAME_CLASS, "min_performance": self.min_performance,
                 "goals": self.goals}
 
@@ -427,8 +412,7 @@ class SafeLifeGame:
             keep_start = (v.start_board[i].clone(), v.state["baseline"][i].clone())
         pool = LevelPool.from_levels([lvl])
         pdev = pool.to_device(v.device)
-        v._may_spawn = v._may_spawn or pool.has_spawners()
-        v._allow_board_bits(v._pool_bits(pool))      # (64x64 planes kept zero)
+        v._admit_pool_boards(pool)
         cfg = v._fill_cfg()
         cfg.level_mode, cfg.augment_roll, cfg.env0, cfg.n_total_envs = 0, 0, 0, 1
         cfg.wrapper_min_performance = float("nan")
@@ -480,7 +464,7 @@ class SafeLifeGame:
         v, i = self._venv, self._idx
         self.rescore()
         v.state["baseline"][i] = v.state["score"][i]
-        v.start_board[i].copy_(v.board[i])
+        v.start_board[i].copy_(v._synced_board()[i])
         v.state["start_roll"][i] = -1
         hi = 4 if ((v.H, v.W) == (128, 128)
                    and bool(start_board_hi_bits(v.start_board[i:i + 1])[0])) else 0

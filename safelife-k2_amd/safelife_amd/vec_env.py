@@ -278,14 +278,76 @@ class SafeLifeVecEnv:
         new = s.board_zero & self._zero_planes(bits)
         if new != s.board_zero:
             self.sync_board()
-            self.planes_ok.bitwise_and_(~(64 | 128))
+            self._pok_clear(_lib.SL_POK_BOARD)
             s.board_zero = new
             s.planes_live = 0
+
+    def _admit_pool_boards(self, pool):
+        """Resets are about to draw boards from `pool` (set_pool; a game's deserialize):
+        their cell bits leave board_zero, and their spawners count.  Running envs keep
+        their boards, so the spawner flag only grows here."""
+        self._allow_board_bits(self._pool_bits(pool))
+        self._may_spawn = self._may_spawn or pool.has_spawners()
 
     def _device_board_bits(self, boards):
         """OR of every cell of a uint16 device tensor (16 reductions; rare events only)."""
         v = boards.view(self.torch.int16)
         return sum(1 << k for k in range(16) if bool(((v >> k) & 1).any().item()))
+
+    # ----------------------------------- planes_ok: state written outside the kernels
+    # What a write from Python does to sl_env_state.planes_ok (the SL_POK_* bits,
+    # include/safelife_hip.h), of env e or of every env.  With _allow_board_bits above,
+    # the only Python code that writes the word.
+    def _pok_clear(self, bits, e=None):
+        (self.planes_ok if e is None else self.planes_ok[e]).bitwise_and_(~bits)
+
+    def _pok_goals_written(self, e=None):
+        """The goals were written: their mirror is stale.  (The board is completed first,
+        which keeps a caller right that clears board bits along with these.)"""
+        self.sync_board()
+        self._pok_clear(_lib.SL_POK_GOALS, e)
+
+    def _pok_board_written(self, e=None):
+        """The uint16 board was written -- completed (sync_board) and board_zero widened
+        (_allow_board_bits) before the write: its planes and draw planes are stale."""
+        self._pok_clear(_lib.SL_POK_ELIG | _lib.SL_POK_BOARD, e)
+
+    def _pok_state_replaced(self, e=None):
+        """Board, goals and scalars were all replaced: no derived copy is valid."""
+        (self.planes_ok if e is None else self.planes_ok[e]).zero_()
+
+    def _pok_stepping_switched(self, e=None):
+        """Between batch and reference stepping (step_env_reference): each keeps the
+        128x128 replay's next-step eligible counts in a scratch of its own, so the draw
+        planes are recounted from the board once."""
+        self._pok_clear(_lib.SL_POK_ELIG, e)
+
+    # -------------------------------------------------- one env's cells, from outside
+    def _cells(self, cells):
+        """`cells` (array or tensor, [H, W]) as a uint16 tensor on the device."""
+        torch = self.torch
+        if not isinstance(cells, torch.Tensor):
+            cells = torch.from_numpy(np.ascontiguousarray(cells, dtype=np.uint16))
+        if tuple(cells.shape) != (self.H, self.W):
+            raise ValueError("board must be %dx%d" % (self.H, self.W))
+        return cells.to(device=self.device, dtype=torch.uint16)
+
+    def write_board(self, e, cells):
+        """Replace env e's board (uint16 [H, W]); scores are the caller's to refresh
+        (sl_env_rescore)."""
+        v = self._cells(cells)
+        self._allow_board_bits(self._device_board_bits(v))
+        self._synced_board()[e].copy_(v)
+        self.st_t["spawn_flags"][e].bitwise_or_(1)      # may now hold a spawner
+        self._may_spawn = True
+        self._pok_board_written(e)
+
+    def write_goals(self, e, cells):
+        """Replace env e's goals (uint16 [H, W]); scores are the caller's to refresh."""
+        self.goals[e].copy_(self._cells(cells))
+        self.st_t["spawn_flags"][e].bitwise_or_(2)
+        self._may_spawn = True
+        self._pok_goals_written(e)
 
     def set_pool(self, levels, pool_dev=None):
         """Replace the level pool the next resets draw from (same board shape).
@@ -299,12 +361,10 @@ class SafeLifeVecEnv:
                              % (pool.H, pool.W, self.H, self.W))
         if pool.K < 1:
             raise ValueError("empty level pool")
-        self._allow_board_bits(self._pool_bits(pool))
+        self._admit_pool_boards(pool)
         self.pool = pool
         self._pool_dev = pool_dev if pool_dev is not None else pool.to_device(self.device)
         self._check_ring_threshold(pool.spawn_prob)
-        # running envs keep their old-pool boards: the flag only grows here
-        self._may_spawn = self._may_spawn or pool.has_spawners()
         # running episodes' start boards are no longer levels of the pool: the
         # kernels read them from HBM until those envs are reset from the new pool
         self.st_t["start_roll"].fill_(-1)
@@ -534,8 +594,8 @@ class SafeLifeVecEnv:
         # keep a reference until the next step
         self._actions_in_flight = a
         L = _lib.lib()
-        if self._last_mode == "reference" and self.planes_ok is not None:
-            self.planes_ok.bitwise_and_(~8)     # (see step_env_reference)
+        if self._last_mode == "reference":
+            self._pok_stepping_switched()
         self._last_mode = "batch"
         cfg = self._fill_cfg()
         self._check_reset_lists()
@@ -622,11 +682,10 @@ class SafeLifeVecEnv:
         if not 0 <= e < self.B:
             raise IndexError("env %d outside [0, %d)" % (e, self.B))
         fr = self._ref_frame()
-        if self._last_mode != "reference" and self.planes_ok is not None:
+        if self._last_mode != "reference":
             # the 128x128 replay keeps each env's next-step eligible count in the scratch
-            # (act[2B + b]); the reference steps keep theirs per env in fr["scratch"],
-            # so the draw planes are recounted from the board once on a switch
-            self.planes_ok.bitwise_and_(~8)
+            # (act[2B + b]); the reference steps keep theirs per env in fr["scratch"]
+            self._pok_stepping_switched()
         self._last_mode = "reference"
         n2 = 2 * self.H * self.W
         fr["draws_h"].numpy()[:] = speedups._buffer.peek(n2)
@@ -763,15 +822,24 @@ class SafeLifeVecEnv:
 
     @property
     def board(self):
-        """uint16 [B, H, W] boards.  A 128x128 batch keeps its boards in bit planes
-        across its steps (sl_env_state.board_planes); reading this always completes the
-        tensor first (sl_env_board_sync, stream-ordered).  Whether an env's uint16 board
-        is complete is decided on the device, per env (planes_ok bits 6-7), never by a
-        host flag: an env whose board is already complete costs its workgroup one load.
-        Write boards through set_state / load_state_dict (or clear planes_ok after
-        writing).  With board_mode="auto" a read also makes the next
-        BOARD_READ_WINDOW steps write the uint16 board themselves."""
+        """uint16 [B, H, W] boards.  A 64x64 or 128x128 batch keeps its boards in bit
+        planes across its steps (sl_env_state.board_planes); reading this always completes
+        the tensor first (sl_env_board_sync, stream-ordered).  Whether an env's uint16
+        board is complete is decided on the device, per env (SL_POK_BOARD_PLANES /
+        SL_POK_BOARD_FULL), never by a host flag: an env whose board is already complete
+        costs its workgroup one load.  Write boards with write_board, set_state or
+        load_state_dict.  A write into this tensor must go through them: the planes
+        still hold the old board (clearing planes_ok drops them), and cell bits new to
+        the batch must first leave board_zero, the planes the kernels neither load nor
+        store, which only those three see to.  With
+        board_mode="auto" a read also makes the next BOARD_READ_WINDOW steps write the
+        uint16 board themselves."""
         self._board_read_at = self._step_index
+        return self._synced_board()
+
+    def _synced_board(self):
+        """`board` for the library's own reads and writes: completed, and not counted
+        as a caller's read (board_mode="auto")."""
         self.sync_board()
         return self._board
 
@@ -819,7 +887,7 @@ class SafeLifeVecEnv:
         hi = start_board_hi_bits(self.start_board) & ((self.H, self.W) == (128, 128))
         self.st_t["spawn_flags"].copy_(3 | 4 * hi.to(self.st_t["spawn_flags"].dtype))
         self._may_spawn = True
-        self.planes_ok.zero_()
+        self._pok_state_replaced()
         self.scratch[8 * self.B + 2:8 * self.B + 4].zero_()
         self._last_step = None
         self._check_ring_threshold()
@@ -828,7 +896,7 @@ class SafeLifeVecEnv:
                         - int(self._running_mask().sum().item()) - self._abandoned)
 
     def state_dict(self):
-        d = {"board": self.board.clone(), "goals": self.goals.clone(),
+        d = {"board": self._synced_board().clone(), "goals": self.goals.clone(),
              "start_board": self.start_board.clone(), "step_index": self._step_index,
              "stream_pos": self.stream_pos.clone()}
         pos = getattr(self.stream_exchange, "pos", None)

@@ -350,3 +350,109 @@ def test_state_dict_keeps_exchange_position(torch_dev):
     ex.pos.zero_()
     v.load_state_dict(sd)
     assert int(ex.pos.item()) == p
+
+
+_SCORE_SCALARS = ("score", "possible", "baseline", "old_points", "side_effect", "episode_reward",
+                  "episode_length", "game_over", "agent_x", "agent_y")
+
+
+def _quiet_patch(board, ay, ax):
+    """Centre (cy, cx) of an empty 5x5 patch of `board` (64x64) whose cells are all at
+    least 8 cells (torus, either axis) from the agent and from every exit, and off rows
+    0, 31, 32 and 63 (the rows the plane kernel treats apart)."""
+    from safelife_amd import CellTypes
+    H, W = board.shape
+    keep_off = [(ay, ax)] + [tuple(p) for p in np.argwhere((board & CellTypes.exit) != 0)]
+
+    def far(c, p, n):          # the patch c-2..c+2 is >= 8 from p
+        d = abs(c - p) % n
+        return min(d, n - d) >= 10
+    for cy in list(range(3, 29)) + list(range(35, 61)):
+        for cx in range(2, W - 2):
+            if board[cy - 2:cy + 3, cx - 2:cx + 3].any():
+                continue
+            if all(far(cy, y, H) or far(cx, x, W) for y, x in keep_off):
+                return cy, cx
+    raise AssertionError("no quiet 5x5 patch")
+
+
+@pytest.mark.parametrize("pool_name,B", [("c3_prune_still_64", 4), ("c5_navigation_128", 3)])
+def test_goals_setter_after_plane_steps_keeps_board(torch_dev, pool_name, B):
+    """Assigning game.goals while the env's board lives only in its planes
+    (SL_POK_BOARD_PLANES without SL_POK_BOARD_FULL) marks the goals mirror stale and
+    nothing else: the steps that follow equal those of a board_mode="uint16" twin, bit
+    for bit.  (The setter used to clear the whole word, and the next step then started
+    from the stale uint16 board.)  At 64x64 the pool's levels are still lifes, so env 1
+    gets a blinker first: a stale board is then a different board."""
+    import torch
+    from safelife_amd import CellTypes, SafeLifeGame, SafeLifeVecEnv, LevelPool, _lib
+    pool = LevelPool.load(os.path.join(GOLDEN, "pools", pool_name + ".npz"))
+    twins = [SafeLifeVecEnv(pool, B, "cuda:0", rng="philox", seed=9, output_channels=None,
+                            penalty_coef=1.0, board_mode=m) for m in ("planes", "uint16")]
+    planes, u16 = twins
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(6)
+    acts = [torch.randint(0, 9, (B,), dtype=torch.int32, device="cuda:0", generator=g)
+            for _ in range(9)]
+    for v in twins:
+        v.reset()
+    patch = None
+    if pool.H == 64:
+        b0 = u16.board[1].cpu().numpy()
+        cy, cx = _quiet_patch(b0, int(u16.state["agent_y"][1].item()),
+                              int(u16.state["agent_x"][1].item()))
+        patch = (slice(cy - 2, cy + 3), slice(cx - 2, cx + 3))
+        b0[cy, cx - 1:cx + 2] = CellTypes.alive | CellTypes.destructible
+        for v in twins:
+            SafeLifeGame(v, 1).board = b0
+
+    def same(t):
+        assert torch.equal(planes.reward, u16.reward), t
+        assert torch.equal(planes.done, u16.done), t
+        for k in _SCORE_SCALARS:
+            assert torch.equal(planes.state[k], u16.state[k]), (t, k)
+
+    before = None
+    for t in range(3):
+        before = u16.board[1].clone()
+        for v in twins:
+            v.step(acts[t])
+        same(t)
+    pok = int(planes.planes_ok[1].item())
+    assert pok & _lib.SL_POK_BOARD_PLANES and not pok & _lib.SL_POK_BOARD_FULL, pok
+    if patch is not None:
+        assert not torch.equal(before[patch], u16.board[1][patch])
+    new_goals = u16.goals[1].cpu().numpy()
+    assert np.array_equal(new_goals, planes.goals[1].cpu().numpy())
+    if patch is not None:
+        new_goals[cy - 1:cy + 2, cx] |= CellTypes.color_b
+    else:
+        new_goals[60:68, 60:68] ^= CellTypes.color_b
+    for v in twins:
+        SafeLifeGame(v, 1).goals = new_goals
+    for t in range(3, 9):
+        for v in twins:
+            v.step(acts[t])
+        same(t)
+        assert torch.equal(planes.board, u16.board), t
+        assert torch.equal(planes.goals, u16.goals), t
+
+
+def test_internal_board_reads_keep_plane_mode(torch_dev):
+    """board_mode="auto" switches to the kernel that writes the uint16 board when the
+    caller reads `board`; the library's own reads (state_dict here) do not count."""
+    import torch
+    from safelife_amd import SafeLifeVecEnv, LevelPool, _lib
+    pool = LevelPool.load(os.path.join(GOLDEN, "pools", "c3_prune_still_64.npz"))
+    v = SafeLifeVecEnv(pool, 2, "cuda:0", rng="philox", seed=2, output_channels=None,
+                       board_mode="auto")
+    v.reset()
+    a = torch.zeros(2, dtype=torch.int32, device="cuda:0")
+    v.step(a)
+    v.step(a)
+    v.state_dict()
+    assert not v._wants_uint16_board()
+    v.step(a)
+    assert int(v.planes_ok[0].item()) & _lib.SL_POK_BOARD_PLANES
+    assert v.board.shape == (2, 64, 64)
+    assert v._wants_uint16_board()
