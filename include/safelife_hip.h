@@ -424,6 +424,20 @@ typedef struct sl_env_state {
                                  entry points run are skipped.  Zero-init; a
                                  caller stepping a slice (a copy of this
                                  struct) ORs the slice's flag back in.         */
+    uint32_t agent_planes;    /* 64x64 plane mode: cell bits (planes) that, in every
+                                 board of the batch and for good, are set in the
+                                 agent's cell (agent_y, agent_x) and in no other
+                                 (the caller's promise: in its levels and written
+                                 boards they sit on the agent's cell alone, that
+                                 cell is frozen, and no birth, spawn, exit or
+                                 allowed toggle sets them).  Their planes are
+                                 neither loaded nor stored: the kernels build them
+                                 from the agent's position, and sl_env_board_sync
+                                 puts them into the completed uint16 board.  Never
+                                 overlaps board_zero.  Changes as board_zero does:
+                                 complete the board first and clear SL_POK_BOARD;
+                                 clearing bits is always safe then.  0 = none.
+                                 128x128 kernels ignore it.                     */
 } sl_env_state;
 
 /*

@@ -778,39 +778,65 @@ k_env_step_bits64(StepKArgs ka) {
 // the wave's buffer at once -- as the uint16 board was -- runs the action on them, and
 // stores only the words that changed; no transposes.  Planes in
 // sl_env_state.board_zero (all zero in every board of the batch, for good: the C3 / C4
-// pools never use cell bits 7 and 11-14) are neither loaded nor stored, and the kept
-// ones are packed (PlaneSlots): 6 of the 8 KiB are read.  SL_POK_BOARD_PLANES: the
+// pools never use cell bits 7 and 11-14) are neither loaded nor stored, nor are the
+// planes in sl_env_state.agent_planes (one cell each, the agent's: built from its
+// position), and the stored ones are packed (PlaneSlots): on C3 / C4 4 of the 8 KiB are
+// read.  SL_POK_BOARD_PLANES: the
 // planes hold the board; SL_POK_BOARD_FULL: so does the uint16 board (a sync wrote it),
 // which a plane step otherwise leaves stale (exits aside: the epilogue writes them in
 // both).
 
-// The planes outside `zero` packed word after word: word q (plane q & 15 of column
-// word q >> 4) at position pos(q), the number of kept words below it, so the kept words
-// come first and one DMA instruction of 16 B per lane moves four of them (C3: 22 of 32
-// words in 6 instructions, where 4-B DMAs word by word took 22 and ran 12 % slower).
-// The layout follows sl_env_state.board_zero, which changes only after every board has
-// left the planes.
-template <u32 K16>       // the kept planes, fixed at compile time; 0: from board_zero
+// The stored planes packed word after word: word q (plane q & 15 of column word q >> 4)
+// at position pos(q), the number of stored words below it, so the stored words come
+// first and one DMA instruction of 16 B per lane moves four of them (4-B DMAs word by
+// word ran 12 % slower).  Two masks: the planes a board can HOLD (~board_zero: the
+// others are zero in registers too) and, among them, the planes that are STORED: held
+// and not in sl_env_state.agent_planes.  An agent plane holds one cell, the agent's, whose
+// position is in the env's record: its words are built from (R_AY, R_AX), never loaded
+// or stored (C3 / C4: planes 1, 5 and 6; 16 of 32 words are stored, four DMA
+// instructions with no padding).  The layout follows board_zero and agent_planes, which
+// change only after every board has left the planes.
+// the instantiations: every plane, the C3 / C4 pools' planes (cell bits 0-6, 8-10, 15,
+// of which the agent's 1, 5, 6 are implied), and any other masks at run time
+constexpr u32 kKeepAll = 0xFFFFu, kKeepC3 = 0x877Fu, kAgentC3 = 0x0062u;
+constexpr u32 kKeepC3Fixed = 0x10000u | kKeepC3;   // the dispatch's: kKeepC3 with kAgentC3
+template <u32 K16>       // the held planes, fixed at compile time; 0: from board_zero
 struct PlaneSlots {
-    u32 keep;           // bit q: word q is kept (K16 == 0)
+    // kKeepC3 fixes the agent planes too (the dispatch checks both); the other two
+    // take them at run time
+    static constexpr bool kFixed = K16 == kKeepC3;
+    u32 keep;           // bit q: word q is held (K16 == 0)
+    u32 store;          // bit q: word q is stored (!kFixed)
     __device__ __forceinline__ u32 keep32() const { return K16 ? K16 * 0x10001u : keep; }
+    __device__ __forceinline__ u32 store32() const {
+        return kFixed ? (K16 & ~kAgentC3) * 0x10001u : store;
+    }
     __device__ __forceinline__ bool kept(int q) const { return (keep32() >> q) & 1u; }
+    __device__ __forceinline__ bool stored(int q) const { return (store32() >> q) & 1u; }
+    // the agent planes (held, not stored)
+    __device__ __forceinline__ u32 agent16() const {
+        return kFixed ? kAgentC3 : (keep32() & ~store32()) & 0xFFFFu;
+    }
     // (at run time recomputed where used: two SALU, not 32 positions held in SGPRs all
-    // kernel long; with K16 a constant)
+    // kernel long; with kFixed a constant)
     __device__ __forceinline__ int pos(int q) const {
-        if (K16) return __builtin_popcount((K16 * 0x10001u) & ((1u << q) - 1u));
-        u32 k = keep;
+        if (kFixed) return __builtin_popcount(store32() & ((1u << q) - 1u));
+        u32 k = store;
         asm volatile("" : "+s"(k));
         return __builtin_popcount(k & ((1u << q) - 1u));
     }
-    __device__ __forceinline__ int kept16() const { return __builtin_popcount(keep32() & 0xFFFFu); }
-    static __device__ __forceinline__ PlaneSlots of(u32 zero) {
-        return PlaneSlots{(~zero & 0xFFFFu) * 0x10001u};
+    __device__ __forceinline__ int stored16() const { return __builtin_popcount(store32() & 0xFFFFu); }
+    static __device__ __forceinline__ PlaneSlots of(u32 zero, u32 agent) {
+        const u32 k = ~zero & 0xFFFFu;
+        return PlaneSlots{k * 0x10001u, (k & ~agent) * 0x10001u};
     }
 };
-// the instantiations: every plane, the C3 / C4 pools' planes (cell bits 0-6, 8-10, 15),
-// and any other mask at run time
-constexpr u32 kKeepAll = 0xFFFFu, kKeepC3 = 0x877Fu;
+// this lane's two words of an agent plane: the one bit of cell (ay, ax)
+__device__ __forceinline__ void agent_words(int ay, int ax, int lane, u32 aw[2]) {
+    const u32 bit = lane == 2 * (ax >> 1) + (ay >> 5) ? 1u << (ay & 31) : 0u;
+    aw[0] = (ax & 1) ? 0u : bit;
+    aw[1] = (ax & 1) ? bit : 0u;
+}
 // the plane kernel's waves per SIMD: five (96 VGPRs; 20 x 8 KiB is the CU's LDS) where
 // the instantiation fits that budget without spills -- the C3 / C4 planes without views
 // (its 10 planes never held are 20 registers fewer); the others spill there (13-24
@@ -820,12 +846,12 @@ constexpr int planes_min_waves(u32 k16, int obs) {
     return (obs == 0 && k16 == kKeepC3) ? kMinWavesPlanes : kMinWaves;
 }
 
-// the kept plane words of an env, DMA'd into the wave's buffer in their packed order
+// the stored plane words of an env, DMA'd into the wave's buffer in their packed order
 // (position p of lane l at buf[p * 64 + l]); no registers held while they are in flight
 template <u32 K16>
 __device__ __forceinline__ void dma_planes(const u32 *__restrict__ bp, PlaneSlots<K16> ps,
                                            lds_u32 *buf, int lane) {
-    const int groups = (2 * ps.kept16() + 3) >> 2;
+    const int groups = (2 * ps.stored16() + 3) >> 2;
     const char *s = reinterpret_cast<const char *>(bp);
 #pragma unroll
     for (int g = 0; g < 8; g++)
@@ -854,7 +880,8 @@ struct NearCells {
         return (u32)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane(k));
     }
 };
-// cell i from the staged planes (this lane's; planes not kept are 0)
+// cell i from the staged planes (this lane's; planes not stored are 0: the caller adds
+// the agent planes to the agent's cell)
 template <u32 K16>
 __device__ __forceinline__ u32 lds_plane_cell(const lds_u32 *buf, PlaneSlots<K16> ps, int i) {
     const int y = i >> 6, x = i & 63;
@@ -864,8 +891,8 @@ __device__ __forceinline__ u32 lds_plane_cell(const lds_u32 *buf, PlaneSlots<K16
     u32 v = 0;
 #pragma unroll
     for (int p = 0; p < 16; p++) {
-        const int pw = ps.pos(p) + (w ? ps.kept16() : 0);
-        if (ps.kept(p)) v |= ((q[pw * 64] >> r) & 1u) << p;
+        const int pw = ps.pos(p) + (w ? ps.stored16() : 0);
+        if (ps.stored(p)) v |= ((q[pw * 64] >> r) & 1u) << p;
     }
     return v;
 }
@@ -902,11 +929,18 @@ __global__ void __launch_bounds__(64) k_board_sync64(sl_env_state st, int demote
     const int pok = __builtin_amdgcn_readfirstlane(st.planes_ok[b]);
     if (!(pok & SL_POK_BOARD_PLANES)) return;
     if (!(pok & SL_POK_BOARD_FULL)) {
-        const PlaneSlots<0> ps = PlaneSlots<0>::of(st.board_zero);
+        const PlaneSlots<0> ps = PlaneSlots<0>::of(st.board_zero, st.agent_planes);
         const u32 *bp = st.planes + b * 4096 + lane;
         u32 P[32];
 #pragma unroll
-        for (int q = 0; q < 32; q++) P[q] = ps.kept(q) ? bp[ps.pos(q) * 64] : 0u;
+        for (int q = 0; q < 32; q++) P[q] = ps.stored(q) ? bp[ps.pos(q) * 64] : 0u;
+        // the agent planes: their one cell, from the agent's position
+        u32 aw[2];
+        agent_words(__builtin_amdgcn_readfirstlane(st.agent_y[b]),
+                    __builtin_amdgcn_readfirstlane(st.agent_x[b]), lane, aw);
+#pragma unroll
+        for (int q = 0; q < 32; q++)
+            if ((ps.agent16() >> (q & 15)) & 1u) P[q] = aw[q >> 4];
         transpose32(P);
         u32 *gb = reinterpret_cast<u32 *>(st.board + b * (int64_t)(N * N)) + (lane & 1) * 1024 +
                   (lane >> 1);
@@ -1040,7 +1074,7 @@ void launch_planes64_chan_k(int esz, unsigned grid, const StepKArgs &ka, hipStre
 
 // the plane kernel with channel views: by the kept planes and the element size
 void launch_planes64_chan(u32 keep, int esz, unsigned grid, const StepKArgs &ka, hipStream_t s) {
-    if (keep == kKeepC3) launch_planes64_chan_k<kKeepC3>(esz, grid, ka, s);
+    if (keep == kKeepC3Fixed) launch_planes64_chan_k<kKeepC3>(esz, grid, ka, s);
     else if (keep == kKeepAll) launch_planes64_chan_k<kKeepAll>(esz, grid, ka, s);
     else launch_planes64_chan_k<0>(esz, grid, ka, s);
 }
@@ -1081,18 +1115,21 @@ int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra 
     } else {
         if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
         if (fx.plane_mode) {
-            const u32 keep = ~st.board_zero & 0xFFFFu;
+            // the <kKeepC3, *> instances fix the agent planes as well: a batch holding
+            // those planes whose agent planes differ takes the run-time instance
+            u32 keep = ~st.board_zero & 0xFFFFu;
+            if (keep == kKeepC3) keep = st.agent_planes == kAgentC3 ? kKeepC3Fixed : 0u;
             const int kind = obs_kind(fx);
             if (kind >= 2) {
                 launch_planes64_chan(keep, obs_esz(kind), grid, ka, s);
             } else if (fx.obs_out) {
-                if (keep == kKeepC3)
+                if (keep == kKeepC3Fixed)
                     hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepC3, 1>), dim3(grid), dim3(64), 0, s, ka);
                 else if (keep == kKeepAll)
                     hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepAll, 1>), dim3(grid), dim3(64), 0, s, ka);
                 else
                     hipLaunchKernelGGL((k_env_step_bits64_planes<0, 1>), dim3(grid), dim3(64), 0, s, ka);
-            } else if (keep == kKeepC3) {
+            } else if (keep == kKeepC3Fixed) {
                 hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepC3, 0>), dim3(grid), dim3(64), 0, s, ka);
             } else if (keep == kKeepAll) {
                 hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepAll, 0>), dim3(grid), dim3(64), 0, s, ka);

@@ -17,7 +17,7 @@
     const int64_t b = blockIdx.x;          // one wave per env
     const int lane = threadIdx.x;
     lds_u32 *buf = (lds_u32 *)&stage[0];
-    const PlaneSlots<K16> ps = PlaneSlots<K16>::of(st.board_zero);
+    const PlaneSlots<K16> ps = PlaneSlots<K16>::of(st.board_zero, st.agent_planes);
     Pre pre;
     issue_pre(st, ka.actions, b, lane, pre);
     // the board's planes, speculatively: an env whose planes do not hold its board (the
@@ -62,7 +62,7 @@
         transpose32(R);
 #pragma unroll
         for (int q = 0; q < 32; q++)
-            if (ps.kept(q)) buf[ps.pos(q) * 64 + lane] = R[q];
+            if (ps.stored(q)) buf[ps.pos(q) * 64 + lane] = R[q];
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
@@ -74,7 +74,10 @@
     int eidx[4];
     u32 eval[4];
     const int ay0 = rec(V, R_AY), ax0 = rec(V, R_AX);
-    const u32 near = lane < 9 ? lds_plane_cell(buf, ps, near_cell_index(lane, ay0, ax0)) : 0u;
+    // (cell 0 is the agent's: the agent planes' bits are there, and in no other cell)
+    const u32 near = lane < 9 ? lds_plane_cell(buf, ps, near_cell_index(lane, ay0, ax0)) |
+                                    (lane == 0 ? ps.agent16() : 0u)
+                              : 0u;
     OverlayT<NearCells> ov;
     ov.src = NearCells{ay0, ax0, near};
     ov.n = 0;
@@ -99,6 +102,8 @@
         // no cell of the batch holds a bit outside the kept planes (board_zero), an
         // edited one included: said here, the planes not kept stay constants below
         if (K16) eval[k] &= K16;
+        // the agent planes are rebuilt from the agent's new position below
+        eval[k] &= ~ps.agent16();
     }
     const RecFields fl = rec_fields(a, V, __builtin_amdgcn_readfirstlane(env.go),
                                     __builtin_amdgcn_readfirstlane(env.ax),
@@ -106,12 +111,22 @@
 
     u32 PB[32];
 #pragma unroll
-    for (int q = 0; q < 32; q++) PB[q] = ps.kept(q) ? buf[ps.pos(q) * 64 + lane] : 0u;
+    for (int q = 0; q < 32; q++) PB[q] = ps.stored(q) ? buf[ps.pos(q) * 64 + lane] : 0u;
     wait_lgkm();
     constexpr u32 KEEP = K16 ? K16 : 0xFFFFu;
     if (roll < 0) dma_board(st.start_board + off, buf, lane);
     else pool_dma<KEEP>(fx.pool, rec(V, R_LI), buf, lane);
     (void)mux_edits(PB, ne, eidx, eval, lane);
+    // the agent planes: one word pair, the bit of the agent's cell after the action (the
+    // rule changes no such cell: the host puts a plane in agent_planes only where the
+    // agent's cell is frozen), read by the rule and the views, never loaded or stored
+    {
+        u32 aw[2];
+        agent_words(fl.ay, fl.ax, lane, aw);
+#pragma unroll
+        for (int q = 0; q < 32; q++)
+            if ((ps.agent16() >> (q & 15)) & 1u) PB[q] = aw[q >> 4];
+    }
     // held: changed cells that held a plane a change clears but never sets
     u32 cb[2], held[2];
     rule_planes(PB, cb, Geo64<SPAWN_PHILOX>{lane, ssrc, 0, 0}, sc, 0u, held);
@@ -165,7 +180,7 @@
     if (!pin || wave_or(dw[0] | dw[1] | d9.w[0] | d9.w[1])) {
 #pragma unroll
         for (int k = 0; k < 16; k++) {
-            if (!ps.kept(k)) continue;
+            if (!ps.stored(k)) continue;
 #pragma unroll
             for (int w = 0; w < 2; w++) {
                 const u32 d = (k == 0 || k == 3 || k == 10 || k == 11) ? dw[w]

@@ -147,6 +147,8 @@ class SafeLifeGame:
 
     @agent_loc.setter
     def agent_loc(self, loc):
+        # (the agent's cell is no longer known to hold the agent planes)
+        self._venv._narrow_agent_planes()
         self._set("agent_x", int(loc[0]) % self.width)
         self._set("agent_y", int(loc[1]) % self.height)
 
@@ -546,6 +548,9 @@ class SafeLifeEnv:
             keep.append(t)
             s.goals = t.data_ptr()
         if agent_loc is not None:
+            # (a board in planes is completed with the game's own agent first: the sync
+            # puts the agent planes on the agent's cell, sl_env_state.agent_planes)
+            v.sync_board()
             t = torch.tensor([int(agent_loc[0]) % v.W, int(agent_loc[1]) % v.H],
                              dtype=torch.int32, device=v.device)
             keep.append(t)

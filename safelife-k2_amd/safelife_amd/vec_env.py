@@ -69,6 +69,36 @@ def zero_planes(bits, can_toggle_powers=False, can_toggle_colors=False):
     return (~can) & 0xFFFF
 
 
+AGENT_PLANE_BITS = 0x0062      # CellTypes.agent | preserving | inhibiting
+
+
+def agent_planes(board, agent_x, agent_y, can_toggle_powers=False):
+    """sl_env_state.agent_planes for levels `board` [K, H, W] whose agents start at
+    (agent_y[k], agent_x[k]): the cell bits that sit on the agent's cell and on no other
+    in every level, for good.  Of CellTypes.player's bits only agent, preserving and
+    inhibiting are candidates (a birth sets destructible; frozen is every wall's); those
+    a power toggle can flip (0x00E1) are out when powers can be toggled.  The agent's
+    cell must be frozen in every level, so that no step of the rule changes it (the
+    step kernels rebuild the planes from the agent's position after the rule)."""
+    board = np.asarray(board, dtype=np.uint16)
+    K = board.shape[0]
+    if K == 0:
+        return 0
+    cand = AGENT_PLANE_BITS & ~(0x00E1 if can_toggle_powers else 0)
+    at = board[np.arange(K), np.asarray(agent_y), np.asarray(agent_x)]
+    if not (at & 0x0010).all():
+        return 0
+    mask = 0
+    for k in range(16):
+        bit = 1 << k
+        if not cand & bit:
+            continue
+        n = ((board & bit) != 0).reshape(K, -1).sum(1)
+        if (n == 1).all() and ((at & bit) != 0).all():
+            mask |= bit
+    return mask
+
+
 def start_board_hi_bits(start_board):
     """Per env: does any start-board cell use bits 12-14 (used by no cell type)?"""
     import torch
@@ -219,6 +249,7 @@ class SafeLifeVecEnv:
             self.board_planes = self.planes
             s.board_planes = self.planes.data_ptr()
             s.board_zero = self._zero_planes(self._pool_bits(self.pool))
+            s.agent_planes = self._agent_planes(self.pool)
         if (H, W) == (128, 128):
             # the 128x128 board in bit planes, kept there by steps without observations
             # or with packed views (sl_env_state.board_planes); `board` completes the
@@ -282,11 +313,30 @@ class SafeLifeVecEnv:
             s.board_zero = new
             s.planes_live = 0
 
+    def _agent_planes(self, pool):
+        """sl_env_state.agent_planes that boards reset from `pool` keep."""
+        return agent_planes(pool.board, pool.agent_x, pool.agent_y, self.can_toggle_powers)
+
+    def _narrow_agent_planes(self, keep=0):
+        """Boards that keep only the agent planes `keep` are about to enter the batch (0: a
+        board or an agent position written from outside, of which nothing is known): the
+        others leave agent_planes, never to return.  Envs kept in planes under the old
+        mask are completed and taken out of plane mode first, as in _allow_board_bits."""
+        s = self._state
+        new = s.agent_planes & keep
+        if new != s.agent_planes:
+            self.sync_board()
+            self._pok_clear(_lib.SL_POK_BOARD)
+            s.agent_planes = new
+            s.planes_live = 0
+
     def _admit_pool_boards(self, pool):
         """Resets are about to draw boards from `pool` (set_pool; a game's deserialize):
-        their cell bits leave board_zero, and their spawners count.  Running envs keep
-        their boards, so the spawner flag only grows here."""
+        their cell bits leave board_zero, agent planes their agents do not keep leave
+        agent_planes, and their spawners count.  Running envs keep their boards, so the
+        spawner flag only grows here."""
         self._allow_board_bits(self._pool_bits(pool))
+        self._narrow_agent_planes(self._agent_planes(pool))
         self._may_spawn = self._may_spawn or pool.has_spawners()
 
     def _device_board_bits(self, boards):
@@ -337,6 +387,7 @@ class SafeLifeVecEnv:
         (sl_env_rescore)."""
         v = self._cells(cells)
         self._allow_board_bits(self._device_board_bits(v))
+        self._narrow_agent_planes()
         self._synced_board()[e].copy_(v)
         self.st_t["spawn_flags"][e].bitwise_or_(1)      # may now hold a spawner
         self._may_spawn = True
@@ -803,7 +854,7 @@ class SafeLifeVecEnv:
         s.B, s.H, s.W = n, self.H, self.W
         for name, _ in _lib.EnvState._fields_[3:]:
             base = getattr(full, name)
-            if name in ("board_zero", "planes_live"):     # (not per-env pointers)
+            if name in ("board_zero", "planes_live", "agent_planes"):   # (not per-env pointers)
                 setattr(s, name, base)
                 continue
             if not base:
@@ -882,6 +933,9 @@ class SafeLifeVecEnv:
         if self._state.board_zero:      # boards written from outside: their bits count
             self._state.board_zero &= self._zero_planes(self._device_board_bits(self._board)
                                                         | self._device_board_bits(self.start_board))
+        # (boards and agents written from outside: no plane is the agent's alone; every
+        # env leaves plane mode below)
+        self._state.agent_planes = 0
         # may hold spawners (replay counts them); bit 2 (128x128 boards): the start board
         # uses cell bits 12-14, which the 128x128 kernel then compares in a second pass
         hi = start_board_hi_bits(self.start_board) & ((self.H, self.W) == (128, 128))
@@ -904,6 +958,10 @@ class SafeLifeVecEnv:
             # parity mode over shards: the global stream position lives in the exchange
             d["exchange_pos"] = pos.clone()
         d.update({k: v.clone() for k, v in self.st_t.items()})
+        # the agent planes these boards keep (a restore into this batch keeps those it
+        # still has itself)
+        d["agent_planes"] = self.torch.tensor(int(self._state.agent_planes),
+                                              dtype=self.torch.int32)
         return d
 
     def load_state_dict(self, d):
@@ -927,4 +985,8 @@ class SafeLifeVecEnv:
             pos.copy_(d["exchange_pos"])
         if self.mt is not None:      # the next step reads from the (global) position on
             self.mt.seek(int((pos if pos is not None else self.stream_pos).item()))
+        # the agent planes the snapshot's boards keep and this batch still has (its pool's,
+        # less what outside writes took); a dict without the entry keeps none
+        ap = self._state.agent_planes & int(d.get("agent_planes", 0))
         self._invalidate_caches()
+        self._state.agent_planes = ap
