@@ -438,6 +438,29 @@ typedef struct sl_env_state {
                                  complete the board first and clear SL_POK_BOARD;
                                  clearing bits is always safe then.  0 = none.
                                  128x128 kernels ignore it.                     */
+    uint32_t goals_gray;      /* 64x64 plane mode, 0 or 1: every goal cell of every
+                                 env of the batch has its three colour bits (9, 10,
+                                 11) equal -- black or white -- and stays so: the
+                                 rule computes each colour plane by the same function
+                                 of the same-numbered plane, actions never edit
+                                 goals, and resets draw from a pool of which the
+                                 same holds (the caller's promise).  Rows black and
+                                 white of the point table are equal and neither
+                                 counts as possible, so with the C3 / C4 planes and
+                                 agent planes (board_zero, agent_planes) the step
+                                 without views reads no goal colour from the mirror
+                                 and the step with packed views one plane of three;
+                                 other plane masks and channel views keep loading
+                                 all three.  The mirror is still written in full
+                                 (resets, the goals' own step): only reads are
+                                 skipped.  Set by the caller from its pool, cleared
+                                 by the caller -- never by the library -- before a
+                                 pool with a coloured goal cell is admitted or the
+                                 goals are written from outside (besides clearing
+                                 SL_POK_GOALS); needs no board sync and no
+                                 planes_ok change; never set again while envs run
+                                 whose goals are not known.  0 = goals of any
+                                 colour.  128x128 kernels ignore it.             */
 } sl_env_state;
 
 /*
@@ -473,7 +496,8 @@ typedef struct sl_env_state {
  *     zero.
  *
  * A caller that writes state from outside the library:
- *   - the goals: clear SL_POK_GOALS;
+ *   - the goals: clear SL_POK_GOALS, and sl_env_state.goals_gray unless every cell
+ *     written is black or white (see there);
  *   - the uint16 board: complete it first (sl_env_board_sync), write, then clear
  *     SL_POK_ELIG | SL_POK_BOARD (and widen board_zero first if the cells written use
  *     planes in it: see there);

@@ -487,18 +487,25 @@ constexpr int obs_esz(int OBS) { return OBS == 3 ? 1 : (OBS == 4 ? 4 : 2); }
 // What an env's step needs first, issued ahead: the per-env record (lane k = field k)
 // and the goals' three colour planes from the mirror (speculative: used when the
 // mirror is valid).  The board itself is DMA'd into the wave's LDS buffer.
+// NG: the colour planes loaded, 3, or fewer for gray goals (sl_env_state.goals_gray, the
+// three planes equal): 1 (plane 9 alone; the others 0) or 0 (no load; all 0).
 struct Pre {
     u32 V;
     u32 g[3][2];
 };
 
+template <int NG = 3>
 __device__ __forceinline__ void issue_pre(const sl_env_state &st, const int32_t *actions,
                                           int64_t b, int lane, Pre &p) {
     p.V = load_record(st, actions, b, lane);
-    if (st.planes) {
+    if (NG < 3) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) p.g[k][0] = p.g[k][1] = 0u;
+    }
+    if (NG > 0 && st.planes) {
         const u32 *mg = st.planes + b * 4096 + 2048 + lane;
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
+        for (int k = 0; k < NG; k++) {
             p.g[k][0] = mg[(9 + k) * 64];
             p.g[k][1] = mg[(25 + k) * 64];
         }
@@ -904,6 +911,23 @@ __global__ void __launch_bounds__(64, planes_min_waves(K16, OBS))
 k_env_step_bits64_planes(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     uint16_t *const vm = nullptr;
+    constexpr bool GRAY = false;
+#include "sl_planes64_step.inc"
+}
+
+// The same for a batch whose goals are all black or white (sl_env_state.goals_gray): the
+// step reads no goal colour plane from the mirror (OBS 0: six loads and six registers
+// fewer, 1 536 of the step's bytes per env) or one of the three (OBS 1, for the view; none
+// with white goals removed).  Instantiated for the C3 / C4 planes only: batches with
+// other plane masks keep loading the colours, gray goals or not.  (Named apart from
+// k_env_step_*, as k_env_planes64_chan is; tests/test_kernel_resources_gray.py.)
+template <u32 K16, int OBS>
+__global__ void __launch_bounds__(64, planes_min_waves(K16, OBS))
+k_env_planes64_gray(StepKArgs ka) {
+    static_assert(OBS <= 1, "channel views load the three colour planes");
+    __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
+    uint16_t *const vm = nullptr;
+    constexpr bool GRAY = true;
 #include "sl_planes64_step.inc"
 }
 
@@ -919,6 +943,7 @@ k_env_planes64_chan(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     __shared__ __attribute__((aligned(16))) uint16_t vmask[sl::obs::kFusedChanCells];
     uint16_t *const vm = vmask;
+    constexpr bool GRAY = false;
 #include "sl_planes64_step.inc"
 }
 
@@ -1122,6 +1147,12 @@ int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra 
             const int kind = obs_kind(fx);
             if (kind >= 2) {
                 launch_planes64_chan(keep, obs_esz(kind), grid, ka, s);
+            } else if (keep == kKeepC3Fixed && st.goals_gray) {
+                // goals all black or white: the instances that skip their colours
+                if (kind)
+                    hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 1>), dim3(grid), dim3(64), 0, s, ka);
+                else
+                    hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 0>), dim3(grid), dim3(64), 0, s, ka);
             } else if (fx.obs_out) {
                 if (keep == kKeepC3Fixed)
                     hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepC3, 1>), dim3(grid), dim3(64), 0, s, ka);

@@ -6,7 +6,9 @@
 // run-time-mask instances by two registers; included, the six older kernels compile to
 // the instructions they had.)  In scope where it is included: the template parameters K16
 // (kept planes; 0: from board_zero) and OBS (k_env_step_bits64's: 0 none, 1 packed views
-// by write_obs, 2-4 channel views by write_obs_channels<obs_esz(OBS)>), the kernel's
+// by write_obs, 2-4 channel views by write_obs_channels<obs_esz(OBS)>), the constant GRAY
+// (k_env_planes64_gray's: sl_env_state.goals_gray holds, every goal cell black or white --
+// the scores read no goal colour, the packed views one plane; OBS <= 1), the kernel's
 // argument `StepKArgs ka`, the wave's buffer `u32 stage[N * N / 2]` in LDS, and `vm`, the
 // view's channel masks in LDS (uint16_t[kFusedChanCells]; unused when OBS < 2).
 // With views, the goal colours are added into planes 12-14 (a bit-sliced adder, exact
@@ -19,7 +21,14 @@
     lds_u32 *buf = (lds_u32 *)&stage[0];
     const PlaneSlots<K16> ps = PlaneSlots<K16>::of(st.board_zero, st.agent_planes);
     Pre pre;
-    issue_pre(st, ka.actions, b, lane, pre);
+    // GRAY: no colour plane for the scores (rows black and white of the point table are
+    // equal, neither counts as possible or as a blue goal: they score as black, 0); the
+    // views add the colours to the board's, so they load one plane for the three -- none
+    // where white goals are removed, which leaves only black ones
+    const bool gray_blank = GRAY && (!OBS || fx.obs_rw != 0);
+    if (!GRAY) issue_pre(st, ka.actions, b, lane, pre);
+    else if (gray_blank) issue_pre<0>(st, ka.actions, b, lane, pre);
+    else issue_pre<1>(st, ka.actions, b, lane, pre);
     // the board's planes, speculatively: an env whose planes do not hold its board (the
     // first step after a host write or a step in another mode) reloads its rows below
     dma_planes(st.planes + b * 4096, ps, buf, lane);
@@ -154,7 +163,8 @@
             if (!((KEEP >> (q & 15)) & 1u)) PS[q] = 0u;
     }
     int pts, scr, pos, side;
-    score_planes(PB, gcol, PS, &pts, &scr, &pos, &side);
+    const u32 gblack[3][2] = {{0u, 0u}, {0u, 0u}, {0u, 0u}};
+    score_planes(PB, GRAY ? gblack : gcol, PS, &pts, &scr, &pos, &side);
     const ScoreTotals tot = score_totals(pts, scr, pos, side);
     __builtin_amdgcn_sched_barrier(0);
 
@@ -196,7 +206,8 @@
         const bool rw = kernarg().fx.obs_rw != 0;
 #pragma unroll
         for (int w = 0; w < 2; w++) {
-            u32 g0 = gcol[0][w], g1 = gcol[1][w], g2 = gcol[2][w];
+            if (GRAY && rw) continue;                // (gray less white: nothing to add)
+            u32 g0 = gcol[0][w], g1 = gcol[GRAY ? 0 : 1][w], g2 = gcol[GRAY ? 0 : 2][w];
             if (rw) {                                // white goals are background
                 const u32 wh = g0 & g1 & g2;
                 g0 &= ~wh;

@@ -51,7 +51,7 @@ class EnvState(ctypes.Structure):
                 ("level_index", vp), ("episodes", vp), ("num_steps", vp),
                 ("spawn_flags", vp), ("start_roll", vp), ("planes", vp), ("planes_ok", vp),
                 ("elig_planes", vp), ("board_planes", vp), ("board_zero", u32),
-                ("planes_live", i32), ("agent_planes", u32)]
+                ("planes_live", i32), ("agent_planes", u32), ("goals_gray", u32)]
 
 
 class LevelPool(ctypes.Structure):

@@ -99,6 +99,17 @@ def agent_planes(board, agent_x, agent_y, can_toggle_powers=False):
     return mask
 
 
+def goals_gray(goals):
+    """sl_env_state.goals_gray for levels whose goals are `goals` [K, H, W]: 1 iff the three
+    colour bits (9, 10, 11) agree in every cell of every level -- every goal black or
+    white.  The rule keeps such goals gray (it computes each colour plane by the same
+    function of the same-numbered plane) and no action edits goals, so the flag holds
+    until a pool with a coloured goal is admitted or the goals are written from outside."""
+    g = np.asarray(goals, dtype=np.uint16)
+    r, gr, b = (g >> 9) & 1, (g >> 10) & 1, (g >> 11) & 1
+    return int(bool(((r == gr) & (r == b)).all()))
+
+
 def start_board_hi_bits(start_board):
     """Per env: does any start-board cell use bits 12-14 (used by no cell type)?"""
     import torch
@@ -250,6 +261,7 @@ class SafeLifeVecEnv:
             s.board_planes = self.planes.data_ptr()
             s.board_zero = self._zero_planes(self._pool_bits(self.pool))
             s.agent_planes = self._agent_planes(self.pool)
+            s.goals_gray = goals_gray(self.pool.goals)
         if (H, W) == (128, 128):
             # the 128x128 board in bit planes, kept there by steps without observations
             # or with packed views (sl_env_state.board_planes); `board` completes the
@@ -330,13 +342,21 @@ class SafeLifeVecEnv:
             s.agent_planes = new
             s.planes_live = 0
 
+    def _narrow_goals_gray(self, keep=0):
+        """Goals are about to enter the batch that are all black or white (keep=1) or of
+        which nothing is known (0: written from outside): goals_gray only ever narrows.
+        No sync and no planes_ok change: the mirror stays complete and current (resets
+        and the goals' step write it in full); the gray kernels only skip reads."""
+        self._state.goals_gray &= int(keep)
+
     def _admit_pool_boards(self, pool):
         """Resets are about to draw boards from `pool` (set_pool; a game's deserialize):
         their cell bits leave board_zero, agent planes their agents do not keep leave
-        agent_planes, and their spawners count.  Running envs keep their boards, so the
-        spawner flag only grows here."""
+        agent_planes, coloured goals end goals_gray, and their spawners count.  Running
+        envs keep their boards, so the spawner flag only grows here."""
         self._allow_board_bits(self._pool_bits(pool))
         self._narrow_agent_planes(self._agent_planes(pool))
+        self._narrow_goals_gray(goals_gray(pool.goals))
         self._may_spawn = self._may_spawn or pool.has_spawners()
 
     def _device_board_bits(self, boards):
@@ -395,6 +415,7 @@ class SafeLifeVecEnv:
 
     def write_goals(self, e, cells):
         """Replace env e's goals (uint16 [H, W]); scores are the caller's to refresh."""
+        self._narrow_goals_gray()
         self.goals[e].copy_(self._cells(cells))
         self.st_t["spawn_flags"][e].bitwise_or_(2)
         self._may_spawn = True
@@ -854,7 +875,8 @@ class SafeLifeVecEnv:
         s.B, s.H, s.W = n, self.H, self.W
         for name, _ in _lib.EnvState._fields_[3:]:
             base = getattr(full, name)
-            if name in ("board_zero", "planes_live", "agent_planes"):   # (not per-env pointers)
+            if name in ("board_zero", "planes_live", "agent_planes",
+                        "goals_gray"):                        # (not per-env pointers)
                 setattr(s, name, base)
                 continue
             if not base:
@@ -936,6 +958,7 @@ class SafeLifeVecEnv:
         # (boards and agents written from outside: no plane is the agent's alone; every
         # env leaves plane mode below)
         self._state.agent_planes = 0
+        self._narrow_goals_gray()        # (goals written from outside: of any colour)
         # may hold spawners (replay counts them); bit 2 (128x128 boards): the start board
         # uses cell bits 12-14, which the 128x128 kernel then compares in a second pass
         hi = start_board_hi_bits(self.start_board) & ((self.H, self.W) == (128, 128))
@@ -962,6 +985,10 @@ class SafeLifeVecEnv:
         # still has itself)
         d["agent_planes"] = self.torch.tensor(int(self._state.agent_planes),
                                               dtype=self.torch.int32)
+        # are these goals all black or white (as agent_planes: kept where the restoring
+        # batch's still are)
+        d["goals_gray"] = self.torch.tensor(int(self._state.goals_gray),
+                                            dtype=self.torch.int32)
         return d
 
     def load_state_dict(self, d):
@@ -988,5 +1015,7 @@ class SafeLifeVecEnv:
         # the agent planes the snapshot's boards keep and this batch still has (its pool's,
         # less what outside writes took); a dict without the entry keeps none
         ap = self._state.agent_planes & int(d.get("agent_planes", 0))
+        gg = self._state.goals_gray & int(d.get("goals_gray", 0))
         self._invalidate_caches()
         self._state.agent_planes = ap
+        self._state.goals_gray = gg
