@@ -63,6 +63,11 @@ extern "C" {
                                 kernel for other shapes                      */
 #define SL_KERNEL_GENERIC 1  /* LDS-staged per-cell kernel, any shape        */
 #define SL_KERNEL_FAST 2     /* require the fast kernel (error if none)      */
+#define SL_KERNEL_BANDS 3    /* bit-sliced rollout, one four-wave workgroup per
+                                board: Philox draws on 128x128 boards;
+                                SL_ETOOBIG elsewhere.  Accepted by
+                                sl_side_effect_densities_k only
+                                (sl_env_cfg.kernel: SL_EINVAL)                */
 
 /* bits of the replay stream's error flag (scratch word 8B, sl_env_cfg.scratch) */
 #define SL_STREAM_ERR_RANGE 1      /* the supplied stream ran out, or the device
@@ -286,10 +291,16 @@ int sl_side_effect_densities(const uint16_t *init_board, const uint16_t *final_b
  *            SL_KERNEL_FAST: the bit-sliced rollout, one wave per board and one launch
  *            per pass (four launches per call) -- Philox draws on 64x64 boards and on
  *            boards of H <= 32, W <= 64; SL_ETOOBIG elsewhere;
- *            SL_KERNEL_AUTO: FAST where it exists (sl_side_effect_kernel), else GENERIC.
- *            The 64x64 kernel loads dwords: 64x64 boards at an address that is no
- *            multiple of 4 go to GENERIC under AUTO and are SL_EINVAL under FAST.
- * Both kernels give the same bytes.  sl_side_effect_densities is
+ *            SL_KERNEL_BANDS: the bit-sliced rollout of 128x128 boards, one workgroup
+ *            of four waves per board (a wave per band of 32 rows, the band in
+ *            registers, one halo row each way through LDS per advance), the same four
+ *            launches per call -- Philox draws on 128x128 boards; SL_ETOOBIG elsewhere;
+ *            SL_KERNEL_AUTO: what sl_side_effect_kernel_auto names: FAST where it
+ *            exists, BANDS on 128x128 boards with Philox draws, else GENERIC.
+ *            The 64x64 and 128x128 kernels load dwords: such boards at an address that
+ *            is no multiple of 4 go to GENERIC under AUTO and are SL_EINVAL under FAST
+ *            or BANDS.
+ * All kernels give the same bytes.  sl_side_effect_densities is
  * _k(..., NULL, SL_KERNEL_AUTO, stream).
  */
 int sl_side_effect_densities_k(const uint16_t *init_board, const uint16_t *final_board,
@@ -301,9 +312,13 @@ int sl_side_effect_densities_k(const uint16_t *init_board, const uint16_t *final
                                double *inaction, double *action, void *workspace,
                                int64_t workspace_bytes, const uint32_t *env_ids, int kernel,
                                void *stream);
-/* SL_KERNEL_FAST if SL_KERNEL_AUTO takes the bit-sliced rollout for such a call, else
+/* SL_KERNEL_FAST if SL_KERNEL_AUTO takes the one-wave rollout for such a call, else
  * SL_KERNEL_GENERIC (host only; no GPU needed) */
 int sl_side_effect_kernel(int H, int W, int rng_mode);
+/* the kernel SL_KERNEL_AUTO launches for such a call: SL_KERNEL_GENERIC, SL_KERNEL_FAST
+ * or SL_KERNEL_BANDS (host only; no GPU needed; boards the dword loads cannot take,
+ * see above, go to GENERIC all the same) */
+int sl_side_effect_kernel_auto(int H, int W, int rng_mode);
 
 /* ------------------------------------------------------------------ envs -- */
 

@@ -224,7 +224,9 @@ constexpr int kDrawSlots = 1024;
 // LDS slots from its exclusive prefix (the counts' bits by ballot + v_mbcnt), lane i
 // of round r evaluates slot 64 r + i (the block number from Geo::block_of) and writes
 // its four compare bits into the slot's top nibble, and the owner reads them back.
-// The wave is the whole workgroup; LDS operations of one wave execute in order.
+// Only the calling wave touches `slots` (the wave is the whole workgroup, or a workgroup
+// of several waves gives each its own kDrawSlots words, as k_rollout_bands128 does), so
+// the wave-scope fences below are enough; LDS operations of one wave execute in order.
 template <class Geo>
 __device__ __forceinline__ void compact_draws(const Geo &g, const u32 elig[2], u32 sp[2],
                                               const SpawnCtx &sc, u32 tensor, lds_u16 *slots) {

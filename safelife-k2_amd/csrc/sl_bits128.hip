@@ -37,7 +37,7 @@
 //  * exits are rewritten by the epilogue after the band stores have completed.
 // Finished envs are queued and reset by a follow-up kernel (k_env_reset_list_wide,
 // one 1024-thread block per env).
-#include "sl_bits.h"
+#include "sl_bits_geo.h"
 #include "sl_env_action.h"
 #include "sl_obs.h"
 
@@ -73,63 +73,7 @@ struct LanePtr {
     __device__ __forceinline__ T *operator+(int i) const { return base + (uint32_t)(i + lane_now()); }
 };
 
-// The rows just outside a band as "planes": element p is a word with bit 31 = bit p
-// of the row above's cell pair and bit 0 = bit p of the row below's, computed where
-// the rule uses it (two registers live instead of the full 32-word array).
-struct HaloView {
-    u32 up, dn;
-    __device__ __forceinline__ u32 operator[](int p) const {
-        return ((up >> p) << 31) | ((dn >> p) & 1u);
-    }
-};
-
-// Neighbourhood of a band word: columns from the neighbouring lanes (2j - 1 is word
-// 1 of lane j - 1, 2j + 2 word 0 of lane j + 1), rows outside the band from the halo
-// (plane k, word w: bit 31 = row 32t - 1, bit 0 = row 32t + 32).
-template <int MODE>
-struct GeoBand {
-    int lane, row0;
-    HaloView hv;
-    StreamSrc src;     // SPAWN_STREAM: the supplied uniforms; pos = the band's first,
-    int64_t pos;       // used = how many the band consumed
-    int used;
-    int count;         // SPAWN_COUNT: this lane's eligible cells
-    lds_u16 *slots;    // SPAWN_PHILOX: compact_draws' queue (kDrawSlots)
-    u32 e[2];          // SPAWN_COUNT: the band's eligible cells; SPAWN_DECIDED: the
-                       // cells k_stream_draw128 decided spawn
-    template <class F>
-    __device__ __forceinline__ V3 vert(const u32 *P, int w, F f) const {
-        return vert_with(f(P, w), f(hv, w));
-    }
-    __device__ __forceinline__ H3 horiz(u32 w0, u32 w1) const {
-        return H3{lane_m1(w1), lane_p1(w0)};
-    }
-    __device__ __forceinline__ bool halo_spawn() const {
-        return (PL(hv, 7, 0) | PL(hv, 7, 1)) != 0u;
-    }
-    // the 2x2 spawn block of band rows y, y + 1 (y even) of the lane's column pair
-    __device__ __forceinline__ u32 block(int y) const {
-        return block_of(lane, y);
-    }
-    __device__ __forceinline__ u32 block_of(int l, int y) const {
-        return (u32)(((row0 + y) >> 1) * (N / 2) + l);
-    }
-    __device__ __forceinline__ void spawn(const u32 elig[2], u32 sp[2], const SpawnCtx &sc,
-                                          u32 tensor) {
-        if (MODE == SPAWN_PHILOX) {
-            philox_spawn_compact(*this, elig, sp, sc, tensor, slots);
-        } else if (MODE == SPAWN_STREAM) {
-            used = stream_draws<false>(elig, sp, sc.thr, src, pos, lane);
-        } else if (MODE == SPAWN_DECIDED) {
-            sp[0] = elig[0] & e[0];
-            sp[1] = elig[1] & e[1];
-        } else {
-            count += __builtin_popcount(elig[0]) + __builtin_popcount(elig[1]);
-            e[0] = elig[0];
-            e[1] = elig[1];
-        }
-    }
-};
+// (the band geometry, GeoBand, and its halo rows, HaloView: sl_bits_geo.h)
 
 // The start-board planes the side-effect term reads (0, 2, 7-11, 15; 12-14 below),
 // from the level pool's bit planes when the env was reset from the pool: row y of

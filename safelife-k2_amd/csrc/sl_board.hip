@@ -466,6 +466,17 @@ extern "C" int sl_side_effect_kernel(int H, int W, int rng_mode) {
                                                                    : SL_KERNEL_GENERIC;
 }
 
+// Whether SL_KERNEL_AUTO takes the four-wave band rollout where it exists (128x128,
+// Philox).  Set by the A/B of DESIGN.md 6.4 (profiles/side_effect_rollout128_ab.json):
+// at E = 1, 64 and 256 the slowest bands run beat the fastest generic run.
+constexpr bool kAutoTakesBands = true;
+
+extern "C" int sl_side_effect_kernel_auto(int H, int W, int rng_mode) {
+    if (rng_mode == SL_RNG_PHILOX && rollout_bands_shape(H, W))
+        return kAutoTakesBands ? SL_KERNEL_BANDS : SL_KERNEL_GENERIC;
+    return sl_side_effect_kernel(H, W, rng_mode);
+}
+
 extern "C" int sl_side_effect_densities(const uint16_t *init_board, const uint16_t *final_board,
                                         const int32_t *num_steps_dev,
                                         const int32_t *num_steps_host,
@@ -495,7 +506,8 @@ extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
                                           double *action, void *workspace,
                                           int64_t workspace_bytes, const uint32_t *env_ids,
                                           int kernel, void *stream) {
-    if (kernel != SL_KERNEL_AUTO && kernel != SL_KERNEL_GENERIC && kernel != SL_KERNEL_FAST)
+    if (kernel != SL_KERNEL_AUTO && kernel != SL_KERNEL_GENERIC && kernel != SL_KERNEL_FAST &&
+        kernel != SL_KERNEL_BANDS)
         return SL_EINVAL;
     if (E < 0 || H < 2 || W < 2 || num_samples < 1 || max_keys < 1 || max_keys > 1024)
         return SL_EINVAL;
@@ -513,12 +525,19 @@ extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
     // the bit-sliced rollout: Philox draws on 64x64 boards and boards up to 32 x 64.  Its
     // 64x64 kernel loads dwords, so 64x64 boards at an address that is no multiple of 4
     // go to the per-cell kernels (SL_KERNEL_FAST: SL_EINVAL); the small kernel reads uint16
-    bool fast = kernel != SL_KERNEL_GENERIC &&
+    bool fast = (kernel == SL_KERNEL_AUTO || kernel == SL_KERNEL_FAST) &&
                 sl_side_effect_kernel(H, W, rng_mode) == SL_KERNEL_FAST;
     if (kernel == SL_KERNEL_FAST && !fast) return SL_ETOOBIG;
-    if (fast && H == 64 && ((((uintptr_t)init_board) | ((uintptr_t)final_board)) & 3)) {
-        if (kernel == SL_KERNEL_FAST) return SL_EINVAL;
-        fast = false;
+    // ... and the four-wave band rollout: Philox draws on 128x128 boards, dword loads too
+    bool bands = rng_mode == SL_RNG_PHILOX && rollout_bands_shape(H, W) &&
+                 (kernel == SL_KERNEL_BANDS ||
+                  (kernel == SL_KERNEL_AUTO &&
+                   sl_side_effect_kernel_auto(H, W, rng_mode) == SL_KERNEL_BANDS));
+    if (kernel == SL_KERNEL_BANDS && !bands) return SL_ETOOBIG;
+    if (((fast && H == 64) || bands) &&
+        ((((uintptr_t)init_board) | ((uintptr_t)final_board)) & 3)) {
+        if (kernel != SL_KERNEL_AUTO) return SL_EINVAL;
+        fast = bands = false;
     }
     hipStream_t s = (hipStream_t)stream;
     const int hw = H * W;
@@ -534,19 +553,21 @@ extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
         max_steps = num_steps_host[e] > max_steps ? num_steps_host[e] : max_steps;
     }
     const int64_t map_elems = E * (int64_t)max_keys * hw;
-    if (fast) {
-        // four launches: mark, compact, count, normalise (sl_rollout_bits.hip); the mark
-        // pass writes every bitmap word, the boards stay where the caller has them
+    if (fast || bands) {
+        // four launches: mark, compact, count, normalise (sl_rollout_bits.hip,
+        // sl_rollout_bits128.hip); the mark pass writes every bitmap word, the boards stay
+        // where the caller has them
+        const auto launch_rollout = bands ? launch_rollout_bands : launch_rollout_bits;
         RolloutArgs ra{init_board, final_board, num_steps_dev, spawn_prob, env_ids, env0, seed,
                        num_samples, H, W, bitmap, keys, n_keys, max_keys, inaction, action};
         if (hipMemsetAsync(inaction, 0, map_elems * 8, s) != hipSuccess ||
             hipMemsetAsync(action, 0, map_elems * 8, s) != hipSuccess)
             return SL_EHIP;
-        if (launch_rollout_bits(ra, E, 0, s)) return SL_EHIP;
+        if (launch_rollout(ra, E, 0, s)) return SL_EHIP;
         hipLaunchKernelGGL(k_density_compact, dim3((unsigned)E), dim3(NT), 0, s, bitmap, max_keys,
                            keys, n_keys, present);
         if (hipGetLastError() != hipSuccess) return SL_EHIP;
-        if (launch_rollout_bits(ra, E, 1, s)) return SL_EHIP;
+        if (launch_rollout(ra, E, 1, s)) return SL_EHIP;
         hipLaunchKernelGGL(k_density_norm, dim3(1024), dim3(NT), 0, s, inaction, action,
                            map_elems, (double)num_samples);
         return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;

@@ -1013,6 +1013,8 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
     if (cfg->stream_phase < 0 || cfg->stream_phase > 2 || (cfg->stream_phase && !replay) ||
         (cfg->stream_phase == 2 && !cfg->stream_base))
         return SL_EINVAL;
+    // (SL_KERNEL_BANDS names a side-effect rollout kernel: no step kernel)
+    if (cfg->kernel == SL_KERNEL_BANDS) return SL_EINVAL;
     const bool bits_ok = cfg->kernel != SL_KERNEL_GENERIC;
     const bool fast = bits_ok && st->H == 64 && st->W == 64;
     const bool fast128 = bits_ok && bits128_shape(*st);

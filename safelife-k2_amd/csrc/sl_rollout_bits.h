@@ -1,5 +1,6 @@
 // sl_rollout_bits.h -- launcher of the bit-sliced side-effect rollout kernels
-// (sl_rollout_bits.hip), called by sl_side_effect_densities_k (sl_board.hip).
+// (sl_rollout_bits.hip, sl_rollout_bits128.hip), called by sl_side_effect_densities_k
+// (sl_board.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,5 +28,13 @@ bool rollout_bits_shape(int H, int W);
 // pass 0: mark every sampled key; pass 1: count every sampled cell into its key's map.
 // One launch of 2E single-wave workgroups each.
 int launch_rollout_bits(const RolloutArgs &a, int64_t E, int pass, hipStream_t s);
+
+// the four-wave band rollout (sl_rollout_bits128.hip) exists for this shape: 128x128,
+// Philox draws only
+bool rollout_bands_shape(int H, int W);
+
+// the same two passes, one launch of 2E four-wave workgroups each; the boards are read
+// as dwords (4-byte aligned)
+int launch_rollout_bands(const RolloutArgs &a, int64_t E, int pass, hipStream_t s);
 
 }  // namespace sl

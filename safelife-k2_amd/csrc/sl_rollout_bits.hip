@@ -20,33 +20,38 @@
 //                   (counts < 2^53: exact in any order).
 // The rollout is deterministic, so pass 1 revisits the boards of pass 0.  No barrier,
 // no cross-wave ordering, no HBM traffic for the board between its load and the end.
-#include "sl_bits_geo.h"
-#include "sl_rollout_bits.h"
+// The loop, the sample and the key (rollout, sample, key_of) are in sl_rollout_bits_dev.h,
+// shared with the four-wave 128x128 kernel (sl_rollout_bits128.hip).
+#include "sl_rollout_bits_dev.h"
 
 using namespace sl;
 using namespace sl::bits;
 
 namespace {
 
-constexpr int kBitmapWords = 2048;      // 65536 keys, one bit each
-
 // the 64x64 layout (Geo64): lane l = 2j + h holds columns 2j, 2j + 1 over rows 32h ..
 struct Lay64 {
+    static constexpr int kThreads = 64;
     int lane;
     __device__ __forceinline__ u32 valid(int) const { return ~0u; }
     __device__ __forceinline__ int cell(int y, int w) const {
         return (32 * (lane & 1) + y) * 64 + 2 * (lane >> 1) + w;
     }
+    template <class Geo>
+    __device__ __forceinline__ void before_step(const u32 *, Geo &, int) const {}
     __device__ __forceinline__ void after_step(u32 *) const {}
 };
 
 // the small layout (GeoSmall): lane j < ceil(W / 2) holds columns 2j, 2j + 1 over all rows
 struct LaySmall {
+    static constexpr int kThreads = 64;
     int lane, W;
     u32 wm0, wm1;        // rows < H of real columns (the odd-W copy word counts nothing)
     bool odd, odd_last;
     __device__ __forceinline__ u32 valid(int w) const { return w ? wm1 : wm0; }
     __device__ __forceinline__ int cell(int y, int w) const { return y * W + 2 * lane + w; }
+    template <class Geo>
+    __device__ __forceinline__ void before_step(const u32 *, Geo &, int) const {}
     // odd W: the last lane's word 1 is a copy of column 0 (lane 0's word 0); what the
     // rule computed for it is replaced by the new column 0
     __device__ __forceinline__ void after_step(u32 *P) const {
@@ -59,92 +64,6 @@ struct LaySmall {
         }
     }
 };
-
-// the density key of a counted cell (density_key, sl_board.hip; c is never 0 here)
-__device__ __forceinline__ u32 key_of(u32 c) {
-    u32 m = c & ~DESTR & 0xFFFFu;
-    const u32 base = m & ~COLORS;
-    if (base == ALIVE || base == (FROZEN | SPAWN)) m |= DESTR;
-    return m;
-}
-
-template <int PASS, class Lay>
-__device__ __forceinline__ void sample(const u32 P[32], const Lay &lay, u32 *lds, int nk,
-                                       double *dens, int hw) {
-#pragma unroll
-    for (int w = 0; w < 2; w++) {
-        u32 nz = 0u;        // c & ~DESTR != 0
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-            if (k != 3) nz |= PL(P, k, w);
-        // (c & (FROZEN | DESTR | MOVABLE)) == FROZEN
-        const u32 fixed = PL(P, 4, w) & ~(PL(P, 3, w) | PL(P, 2, w) | PL(P, 15, w));
-        u32 m = nz & ~fixed & ~PL(P, 1, w) & lay.valid(w);
-        while (m) {
-            const int y = __builtin_ctz(m);
-            m &= m - 1;
-            u32 c = 0u;
-#pragma unroll
-            for (int k = 0; k < 16; k++) c |= ((PL(P, k, w) >> y) & 1u) << k;
-            const u32 key = key_of(c);
-            if (PASS == 0) {
-                atomicOr(&lds[key >> 5], 1u << (key & 31));
-            } else {
-                const uint16_t *kl = reinterpret_cast<const uint16_t *>(lds);
-                int lo = 0, hi = nk - 1;             // keys ascending
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (kl[mid] < key) lo = mid + 1;
-                    else hi = mid;
-                }
-                if (nk > 0 && kl[lo] == key)         // else: key overflow (n_keys > max_keys)
-                    atomicAdd(&dens[(int64_t)lo * hw + lay.cell(y, w)], 1.0);
-            }
-        }
-    }
-}
-
-template <int PASS, class Geo, class Lay>
-__device__ __forceinline__ void rollout(u32 P[32], Geo &geo, const Lay &lay,
-                                        const RolloutArgs &a, int64_t bi, u32 *lds) {
-    const int64_t e = bi >> 1;
-    const int which = (int)(bi & 1);
-    const int lane = threadIdx.x;
-    const int hw = a.H * a.W;
-    const int st = __builtin_amdgcn_readfirstlane(a.steps[e]);
-    const int first = which == 0 ? st : 0, n_adv = first + a.S;
-    int nk = 0;
-    double *dens = nullptr;
-    if (PASS == 0) {
-        for (int i = lane; i < kBitmapWords; i += 64) lds[i] = 0u;
-    } else {
-        nk = __builtin_amdgcn_readfirstlane(a.n_keys[e]);
-        nk = nk < a.max_keys ? nk : a.max_keys;
-        uint16_t *kl = reinterpret_cast<uint16_t *>(lds);
-        for (int k = lane; k < nk; k += 64) kl[k] = a.keys[e * a.max_keys + k];
-        dens = (which == 0 ? a.inaction : a.action) + e * (int64_t)a.max_keys * hw;
-    }
-    __syncthreads();        // one wave per workgroup: orders the LDS fill, nothing else
-    SpawnCtx sc;
-    sc.gid = a.env_ids ? a.env_ids[e] : a.env0 + (uint32_t)e;
-    sc.gid = (uint32_t)__builtin_amdgcn_readfirstlane((int)sc.gid);
-    sc.seed = a.seed;
-    set_spawn_prob(sc, a.spawn_prob[e]);
-    const u32 tensor = 4u + (u32)which;
-#pragma unroll 1
-    for (int it = 0; it < n_adv; it++) {
-        sc.step = (uint32_t)it;
-        u32 chg[2];
-        rule_planes(P, chg, geo, sc, tensor);
-        lay.after_step(P);
-        if (it >= first) sample<PASS>(P, lay, lds, nk, dens, hw);
-    }
-    if (PASS == 0) {
-        __syncthreads();
-        uint32_t *row = a.bitmap + bi * kBitmapWords;
-        for (int i = lane; i < kBitmapWords; i += 64) row[i] = lds[i];
-    }
-}
 
 template <int PASS>
 __global__ void __launch_bounds__(64)

@@ -15,6 +15,7 @@ CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 SL_OK, SL_EINVAL, SL_EHIP, SL_ETOOBIG = 0, -1, -2, -3
 SL_RNG_STREAM, SL_RNG_PHILOX = 0, 1
 SL_KERNEL_AUTO, SL_KERNEL_GENERIC, SL_KERNEL_FAST = 0, 1, 2
+SL_KERNEL_BANDS = 3     # sl_side_effect_densities_k only: the 128x128 four-wave rollout
 SL_STREAM_ERR_RANGE, SL_STREAM_ERR_THRESHOLD = 1, 2
 SL_BOARD_AUTO, SL_BOARD_UINT16 = 0, 1
 SL_MAX_EXITS = 8
@@ -142,6 +143,9 @@ def lib():
         L.sl_side_effect_densities_k.restype = ctypes.c_int
         L.sl_side_effect_kernel.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.sl_side_effect_kernel.restype = ctypes.c_int
+    if hasattr(L, "sl_side_effect_kernel_auto") or LIB_PATH == _DEFAULT_LIB:
+        L.sl_side_effect_kernel_auto.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.sl_side_effect_kernel_auto.restype = ctypes.c_int
     L.sl_env_obs.argtypes = [ctypes.POINTER(EnvState), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                              ctypes.c_int, vp, ctypes.c_int, vp, vp]
     L.sl_sample_actions.argtypes = [vp, ctypes.c_int, i64, ctypes.c_int, i64, ctypes.c_int, vp,

@@ -34,8 +34,11 @@ def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_
     uniform stream ``spawn_stream`` starting at ``stream_pos``).
     kernel: 'fast' requires the bit-sliced rollout (one wave per board, four launches per
     call: Philox draws on 64x64 boards and boards of H <= 32, W <= 64; raises elsewhere),
-    'generic' the per-cell kernels (one launch per advance), 'auto' takes 'fast' where it
-    exists.  Both give the same bytes.
+    'bands' the bit-sliced rollout of 128x128 boards (four waves per board, one per band
+    of 32 rows, the same four launches: Philox draws on 128x128 boards; raises elsewhere),
+    'generic' the per-cell kernels (one launch per advance), 'auto' takes 'fast' or 'bands'
+    where they exist (``sl_side_effect_kernel_auto`` names the choice).  All give the same
+    bytes.
     env_ids: [E] Philox env ids, one per episode (default env0 + e), so an episode draws
     the same whatever batch it is scored in.
     Returns a list of (inaction, action) dicts, one per episode.
@@ -60,7 +63,7 @@ def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_
                          device=dev)
     mode = {"philox": _lib.SL_RNG_PHILOX, "stream": _lib.SL_RNG_STREAM}[rng]
     kern = {"auto": _lib.SL_KERNEL_AUTO, "generic": _lib.SL_KERNEL_GENERIC,
-            "fast": _lib.SL_KERNEL_FAST}[kernel]
+            "fast": _lib.SL_KERNEL_FAST, "bands": _lib.SL_KERNEL_BANDS}[kernel]
     ids = None
     if env_ids is not None:
         ids_h = np.ascontiguousarray(np.asarray(env_ids, dtype=np.int64).reshape(-1))
@@ -177,8 +180,9 @@ def earth_mover_distance(a, b, metric="manhattan", wrap_x=True, wrap_y=True, tan
 def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
                        include=None, exclude=None, **rollout_kw):
     """side_effects.py:95-161 for E finished episodes: one device call for all rollouts
-    (``side_effect_densities``; ``rollout_kw`` goes to it: rng, seed, env_ids, kernel,
-    ...), then the host EMD per episode and key.  Returns a list of
+    (``side_effect_densities``; ``rollout_kw`` goes to it: rng, seed, env_ids, kernel
+    ('auto', 'generic', 'fast', 'bands'), ...), then the host EMD per episode and key.
+    Returns a list of
     {key: [emd, sum(inaction density)]}, one per episode."""
     init_boards = np.asarray(init_boards) if not hasattr(init_boards, "dim") else init_boards
     shape = tuple(int(x) for x in init_boards.shape[-2:])
@@ -199,7 +203,8 @@ def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_sam
 def side_effect_score(game, num_samples=1000, include=None, exclude=None, **kw):
     """side_effects.py:95-161 for one game-like object (``_init_data['board']``,
     ``board``, ``num_steps``, ``spawn_prob``): {key: [emd, sum(inaction density)]}.
-    The rollout runs on the GPU (``side_effect_densities``); ``kw`` selects its RNG.
+    The rollout runs on the GPU (``side_effect_densities``); ``kw`` selects its RNG and
+    its kernel ('auto', 'generic', 'fast', or 'bands' for 128x128 boards).
     The E = 1 case of ``side_effect_scores``."""
     score, = side_effect_scores(game._init_data["board"][None], game.board[None],
                                 [game.num_steps], game.spawn_prob, num_samples, include,
