@@ -30,6 +30,8 @@
  *                       recenter_view (helper_utils.py:41-74)
  *   sl_side_effect_densities  side_effect_score's rollout + density maps
  *                       (side_effects.py:59-92,131-139), batched over episodes
+ *   sl_side_effect_problem_counts / _cells  earth_mover_distance's changed-cell
+ *                       selection (side_effects.py:36-43) on those maps, on the device
  *   sl_level_pool_prepare  derived pool data for the device level pool
  *                       (levels as loaded by safelife_game.py:184-212)
  *   sl_sample_actions   np.random.choice(len(policy), p=policy) per env in
@@ -319,6 +321,58 @@ int sl_side_effect_kernel(int H, int W, int rng_mode);
  * or SL_KERNEL_BANDS (host only; no GPU needed; boards the dword loads cannot take,
  * see above, go to GENERIC all the same) */
 int sl_side_effect_kernel_auto(int H, int W, int rng_mode);
+
+/*
+ * The EMD problems of side_effect_score, cut from the dense maps on the device
+ * (earth_mover_distance's cell selection, side_effects.py:36-56: the cells where the
+ * two maps differ by more than 1e-3 of their largest difference, row-major).
+ * inaction / action / n_keys are what sl_side_effect_densities_k wrote.  Problem
+ * e * max_keys + k is episode e's key slot k, for k < min(n_keys[e], max_keys); the
+ * other slots are never read and have 0 cells and mass 0.  H, W >= 2, H * W <= 32768,
+ * 1 <= max_keys <= 1024; E == 0 is SL_OK and touches nothing.
+ *
+ * sl_side_effect_problem_counts (side_effects.py:36-41): per problem the number of
+ * selected cells -- |a - b| > 1e-3 * max |a - b|, strictly, the IEEE operations numpy
+ * performs; none when the maps are equal -- scanned into
+ *   offsets  dev int64 [E * max_keys + 1]: problem i owns cells offsets[i] ..
+ *            offsets[i + 1]; the last entry is the total (the scan runs over the counts
+ *            plus one trailing zero)
+ *   mass     dev double [E * max_keys]: the inaction map's sum (side_effects.py:158's
+ *            np.sum up to summation order: per-thread strided sums, a wave butterfly,
+ *            four wave sums in order; see sl_side_effect_problems.hip)
+ *   workspace  dev scratch of sl_side_effect_problems_workspace() bytes, 8-byte aligned;
+ *            keeps each problem's threshold for the fill pass
+ *
+ * sl_side_effect_problem_cells (side_effects.py:41,56): with the same maps, offsets and
+ * workspace, stores problem i's cells in row-major order at offsets[i] + rank:
+ *   p, q     dev double [cap]: the inaction / action density at the cell
+ *   ys, xs   dev int32 [cap]: its row and column
+ *   cap      the buffers' length (the total of offsets); nothing is stored at or
+ *            beyond cap
+ */
+int sl_side_effect_problems_workspace(int64_t E, int max_keys, int64_t *bytes);
+int sl_side_effect_problem_counts(const double *inaction, const double *action,
+                                  const int32_t *n_keys, int64_t E, int max_keys, int H, int W,
+                                  int64_t *offsets, double *mass, void *workspace,
+                                  int64_t workspace_bytes, void *stream);
+int sl_side_effect_problem_cells(const double *inaction, const double *action,
+                                 const int32_t *n_keys, int64_t E, int max_keys, int H, int W,
+                                 const int64_t *offsets, double *p, double *q, int32_t *ys,
+                                 int32_t *xs, int64_t cap, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
+/*
+ * nprob earth mover's distances at once (host code; no GPU needed): problem i is the
+ * cells offsets[i] .. offsets[i + 1] of p, q, ys, xs (host arrays; offsets host int64
+ * [nprob + 1], non-decreasing), and out[i] (host double [nprob]) is exactly what
+ * sl_emd_cells returns for that slice (side_effects.py:36-56), 0 for an empty one.
+ * Runs on min(nthreads, nprob) std::threads (the caller's included), nthreads >= 1;
+ * nprob == 0 is SL_OK; otherwise every pointer must be non-null, also when no problem has
+ * a cell.  Returns the code of the lowest-numbered failing problem (SL_ETOOBIG: out of
+ * memory); a thread that cannot be started is done without.
+ */
+int sl_emd_cells_batch(const double *p, const double *q, const int32_t *ys, const int32_t *xs,
+                       const int64_t *offsets, int64_t nprob, const double *cost_table,
+                       int H, int W, double extra_mass_penalty, double *out, int nthreads);
 
 /* ------------------------------------------------------------------ envs -- */
 

@@ -31,9 +31,11 @@
 // Checked against an exact LP of the same fixed-point problem
 // (tests/test_side_effects_cpu.py).
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 #include "../../include/safelife_hip.h"
@@ -321,4 +323,59 @@ extern "C" int sl_emd_cells(const double *p, const double *q, const int32_t *ys,
     dist += (maxSum - minSum) * extra_mass_penalty;
     *out = dist;
     return SL_OK;
+}
+
+// nprob independent problems on up to nthreads threads.  sl_emd_cells keeps no static or
+// global state (every buffer above is a local), so the threads share nothing but the
+// read-only inputs, the work counter and the error slot; each out[i] is written by the
+// one thread that took problem i.  Problems are handed out one at a time in index order:
+// their cost grows faster than their cell count, so equal shares would not balance.
+extern "C" int sl_emd_cells_batch(const double *p, const double *q, const int32_t *ys,
+                                  const int32_t *xs, const int64_t *offsets, int64_t nprob,
+                                  const double *cost_table, int H, int W,
+                                  double extra_mass_penalty, double *out, int nthreads) {
+    if (nprob < 0 || nthreads < 1 || H < 1 || W < 1) return SL_EINVAL;
+    if (nprob == 0) return SL_OK;
+    if (!p || !q || !ys || !xs || !offsets || !cost_table || !out) return SL_EINVAL;
+    if (offsets[0] < 0) return SL_EINVAL;
+    for (int64_t i = 0; i < nprob; i++)
+        if (offsets[i + 1] < offsets[i]) return SL_EINVAL;
+    std::atomic<int64_t> next(0), first_bad(nprob);
+    std::vector<int> rcs;
+    try {
+        rcs.assign(nprob, SL_OK);
+    } catch (...) {
+        return SL_ETOOBIG;
+    }
+    auto work = [&]() {
+        for (;;) {
+            const int64_t i = next.fetch_add(1, std::memory_order_relaxed);
+            if (i >= nprob) return;
+            const int64_t o = offsets[i];
+            try {
+                rcs[i] = sl_emd_cells(p + o, q + o, ys + o, xs + o, offsets[i + 1] - o,
+                                      cost_table, H, W, extra_mass_penalty, out + i);
+            } catch (...) {                   // out of memory in a problem's buffers
+                rcs[i] = SL_ETOOBIG;
+            }
+            if (rcs[i] != SL_OK) {
+                int64_t seen = first_bad.load();
+                while (i < seen && !first_bad.compare_exchange_weak(seen, i)) {
+                }
+            }
+        }
+    };
+    // no exception leaves this C entry: a thread that cannot be started is done without
+    // (the threads already running and the caller take its problems)
+    const int nt = (int)std::min<int64_t>(nthreads, nprob);
+    std::vector<std::thread> pool;
+    try {
+        pool.reserve(nt);
+        for (int t = 1; t < nt; t++) pool.emplace_back(work);
+    } catch (...) {
+    }
+    work();                                   // the caller is the pool's first thread
+    for (auto &th : pool) th.join();
+    const int64_t bad = first_bad.load();     // the lowest failing problem's code
+    return bad < nprob ? rcs[bad] : SL_OK;
 }

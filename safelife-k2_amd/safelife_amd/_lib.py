@@ -153,6 +153,18 @@ def lib():
     L.sl_gae.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, i64, f64, vp, vp, vp]
     L.sl_emd_cells.argtypes = [vp, vp, vp, vp, i64, vp, ctypes.c_int, ctypes.c_int, f64,
                                ctypes.POINTER(f64)]
+    problems = {"sl_side_effect_problems_workspace": [i64, ctypes.c_int, ctypes.POINTER(i64)],
+                "sl_side_effect_problem_counts": [vp, vp, vp, i64, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int, vp, vp, vp, i64, vp],
+                "sl_side_effect_problem_cells": [vp, vp, vp, i64, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, i64,
+                                                 vp],
+                "sl_emd_cells_batch": [vp, vp, vp, vp, vp, i64, vp, ctypes.c_int, ctypes.c_int,
+                                       f64, vp, ctypes.c_int]}
+    for name, args in problems.items():
+        if hasattr(L, name) or LIB_PATH == _DEFAULT_LIB:
+            getattr(L, name).argtypes = args
+            getattr(L, name).restype = ctypes.c_int
     game = {"sl_env_action": [ctypes.POINTER(EnvState), vp, ctypes.c_int, ctypes.c_int, vp, vp],
             "sl_env_advance": [ctypes.POINTER(EnvState), ctypes.POINTER(EnvCfg), vp],
             "sl_env_rescore": [ctypes.POINTER(EnvState), vp, vp],

@@ -13,6 +13,9 @@ forced are kept and returned by the next call) copies the ring to the host once,
 the finished episodes from the step flags, scores all of them in ONE device call
 (``side_effect_scores``: the bit-sliced rollout where the board shape has one) and
 writes one YAML record each; ``benchmarking.load_benchmarks`` reads the file back.
+``scoring="device"`` copies only the flags and the scalar fields, gathers the finished
+episodes' boards on the device and scores them there up to the EMD inputs
+(``side_effect_scores(..., problems="device")``); only those boards come back.
 
 This is meant for evaluation batches: a step with a capture attached leaves plane mode
 (the board is kept as uint16 cells so it can be copied), and the ring holds
@@ -87,6 +90,13 @@ class EpisodeLog:
     level_titles: names by pool level index (default ``level-<index>``);
     other_episode_data: {key: number or callable(global step count)} added to every
     record; ring: step slots captured between two flushes.
+    scoring: 'host' copies the whole ring to the host at a flush and scores from there;
+    'device' copies only the step flags and the scalar fields, gathers the finished
+    episodes' boards on the device, scores them with
+    ``side_effect_scores(..., problems="device")`` and copies just those boards back
+    (the pinned host mirrors of the two board rings are not allocated).  Same records,
+    same order; the side-effect EMDs are the same bits, the inaction sums may differ in
+    the last bits (``side_effect_scores``).
     """
 
     _FIELDS = (("score", "int32"), ("possible", "int32"), ("baseline", "int32"),
@@ -95,7 +105,10 @@ class EpisodeLog:
                ("episode_reward", "int32"), ("level_index", "int32"))
 
     def __init__(self, venv, log_file=None, record_side_effects=True, num_samples=1000,
-                 side_effect_seed=0, level_titles=None, other_episode_data=None, ring=64):
+                 side_effect_seed=0, level_titles=None, other_episode_data=None, ring=64,
+                 scoring="host"):
+        if scoring not in ("host", "device"):
+            raise ValueError("scoring must be 'host' or 'device', not %r" % (scoring,))
         if not venv.auto_reset:
             raise ValueError("EpisodeLog needs auto_reset=True (episodes are cut at the "
                              "resets inside sl_env_step)")
@@ -114,6 +127,7 @@ class EpisodeLog:
         if R < 1:
             raise ValueError("ring must hold at least one step")
         self.R = R
+        self.scoring = scoring
         self._ids = torch.arange(B, dtype=torch.int32, device=dev)
         self._board = torch.zeros((R, B, H, W), dtype=torch.uint16, device=dev)
         self._start = torch.zeros((R, B, H, W), dtype=torch.uint16, device=dev)
@@ -122,7 +136,8 @@ class EpisodeLog:
                    for k, dt in self._FIELDS}
         # pinned host mirrors of the ring: a flush is async copies and one stream sync
         self._host = {k: torch.zeros(t.shape, dtype=t.dtype).pin_memory()
-                      for k, t in self._ring().items()}
+                      for k, t in self._ring().items()
+                      if scoring == "host" or k not in ("board", "start")}
         self._cap = _lib.Capture()
         self._slot = 0
         self._pending = []           # records of the flushes the full ring forced
@@ -173,8 +188,9 @@ class EpisodeLog:
         if S == 0:
             return
         v = self.venv
-        for k, t in self._ring().items():
-            self._host[k][:S].copy_(t[:S], non_blocking=True)
+        ring = self._ring()
+        for k, m in self._host.items():
+            m[:S].copy_(ring[k][:S], non_blocking=True)
         v.torch.cuda.current_stream(v.device).synchronize()
         fl = self._host["flags"][:S].numpy()
         ss, ii = np.nonzero(fl & 4)              # slot-major: the order the episodes ended
@@ -182,16 +198,24 @@ class EpisodeLog:
             return
         done = list(zip(ss.tolist(), ii.tolist()))
         h = {k: self._host[k][:S].numpy()[ss, ii] for k in self._t}
-        starts_h = self._host["start"][:S].numpy()[ss, ii]
-        boards_h = self._host["board"][:S].numpy()[ss, ii]
+        if self.scoring == "device":
+            # the finished episodes' boards, gathered on the device (indexed as int16: the
+            # same bytes) and copied back alone
+            si, ei = (v.torch.from_numpy(a).to(v.device) for a in (ss, ii))
+            starts = self._start.view(v.torch.int16)[si, ei].view(v.torch.uint16)
+            boards = self._board.view(v.torch.int16)[si, ei].view(v.torch.uint16)
+            starts_h, boards_h = starts.cpu().numpy(), boards.cpu().numpy()
+        else:
+            starts = starts_h = self._host["start"][:S].numpy()[ss, ii]
+            boards = boards_h = self._host["board"][:S].numpy()[ss, ii]
         gids = [v.env0 + int(i) for i in ii]
         scores = None
         if self.record_side_effects:
             from .side_effects import side_effect_scores
-            scores = side_effect_scores(starts_h, boards_h, h["num_steps"], h["spawn_prob"],
+            scores = side_effect_scores(starts, boards, h["num_steps"], h["spawn_prob"],
                                         self.num_samples, rng="philox",
                                         seed=self.side_effect_seed, env_ids=gids,
-                                        device=v.device)
+                                        device=v.device, problems=self.scoring)
         step_count = v.global_counter.num_steps
         other = {k: float(val(step_count) if callable(val) else val)
                  for k, val in self.other_episode_data.items()}

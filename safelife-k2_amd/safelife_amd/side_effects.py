@@ -14,35 +14,32 @@ absent here).  The EMD is FastEMD's emd_hat (what ``pyemd.emd`` computes), solve
 exactly by a transportation simplex in host C++ (``sl_emd_cells``,
 csrc/sl_emd.cpp) over a per-offset ground-distance table.
 Parity unpinned: no pyemd output exists in this environment to compare against.
+
+By default (``problems="host"``) both dense map tensors are copied to the host and every
+EMD's cells are selected there with numpy.  ``problems="device"`` selects them where the
+maps are (``side_effect_problems``: ``sl_side_effect_problem_counts`` / ``_cells``,
+csrc/sl_side_effect_problems.hip), copies only the selected cells, their keys and the
+inaction maps' sums, and solves all EMDs in one ``sl_emd_cells_batch`` call.  The EMDs
+are the same bits; the sums may differ from ``np.sum`` in the last bits.
 """
 import ctypes
+import os
 
 import numpy as np
 
 from . import _lib
 
 
-def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
-                          rng="philox", seed=0, env0=0, spawn_stream=None, stream_pos=0,
-                          max_keys=64, device=None, return_stream_pos=False, kernel="auto",
-                          env_ids=None):
-    """Density maps of E episodes' counterfactual (inaction) and actual rollouts.
+class _Rollout:
+    """What the device half of a call leaves in device memory (``_rollout_device``)."""
+    __slots__ = ("E", "H", "W", "dev", "max_keys", "keys", "n_keys", "present", "inaction",
+                 "action", "pos")
 
-    init_boards, final_boards: [E, H, W] (numpy or torch) -- game._init_data['board']
-    and game.board; num_steps: [E] ints (game.num_steps); spawn_prob: scalar or [E].
-    rng: 'philox' (batched) or 'stream' (E == 1: the reference's draw order from the
-    uniform stream ``spawn_stream`` starting at ``stream_pos``).
-    kernel: 'fast' requires the bit-sliced rollout (one wave per board, four launches per
-    call: Philox draws on 64x64 boards and boards of H <= 32, W <= 64; raises elsewhere),
-    'bands' the bit-sliced rollout of 128x128 boards (four waves per board, one per band
-    of 32 rows, the same four launches: Philox draws on 128x128 boards; raises elsewhere),
-    'generic' the per-cell kernels (one launch per advance), 'auto' takes 'fast' or 'bands'
-    where they exist (``sl_side_effect_kernel_auto`` names the choice).  All give the same
-    bytes.
-    env_ids: [E] Philox env ids, one per episode (default env0 + e), so an episode draws
-    the same whatever batch it is scored in.
-    Returns a list of (inaction, action) dicts, one per episode.
-    """
+
+def _rollout_device(init_boards, final_boards, num_steps, spawn_prob, num_samples, rng, seed,
+                    env0, spawn_stream, stream_pos, max_keys, device, kernel, env_ids):
+    """The device part ``side_effect_densities`` and ``side_effect_problems`` share: upload,
+    ``sl_side_effect_densities_k``; nothing is synchronised or copied back."""
     import torch
     dev = _lib.require_device(device)
     L = _lib.lib()
@@ -91,12 +88,47 @@ def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_
         keys.data_ptr(), n_keys.data_ptr(), present.data_ptr(), inaction.data_ptr(),
         action.data_ptr(), ws.data_ptr(), int(nbytes.value), _lib.ptr(ids), kern,
         _lib.stream_ptr(dev)), "sl_side_effect_densities")
-    nk = n_keys.cpu().numpy()
+    r = _Rollout()
+    r.E, r.H, r.W, r.dev, r.max_keys = E, H, W, dev, int(max_keys)
+    r.keys, r.n_keys, r.present, r.inaction, r.action, r.pos = (keys, n_keys, present, inaction,
+                                                                action, pos)
+    return r
+
+
+def _check_key_count(nk, max_keys):
     if (nk > max_keys).any():
         raise ValueError("more than max_keys=%d cell types in a rollout (%d): raise max_keys"
                          % (max_keys, int(nk.max())))
-    keys_h, pres_h = keys.cpu().numpy(), present.cpu().numpy()
-    ina_h, act_h = inaction.cpu().numpy(), action.cpu().numpy()
+
+
+def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
+                          rng="philox", seed=0, env0=0, spawn_stream=None, stream_pos=0,
+                          max_keys=64, device=None, return_stream_pos=False, kernel="auto",
+                          env_ids=None):
+    """Density maps of E episodes' counterfactual (inaction) and actual rollouts.
+
+    init_boards, final_boards: [E, H, W] (numpy or torch) -- game._init_data['board']
+    and game.board; num_steps: [E] ints (game.num_steps); spawn_prob: scalar or [E].
+    rng: 'philox' (batched) or 'stream' (E == 1: the reference's draw order from the
+    uniform stream ``spawn_stream`` starting at ``stream_pos``).
+    kernel: 'fast' requires the bit-sliced rollout (one wave per board, four launches per
+    call: Philox draws on 64x64 boards and boards of H <= 32, W <= 64; raises elsewhere),
+    'bands' the bit-sliced rollout of 128x128 boards (four waves per board, one per band
+    of 32 rows, the same four launches: Philox draws on 128x128 boards; raises elsewhere),
+    'generic' the per-cell kernels (one launch per advance), 'auto' takes 'fast' or 'bands'
+    where they exist (``sl_side_effect_kernel_auto`` names the choice).  All give the same
+    bytes.
+    env_ids: [E] Philox env ids, one per episode (default env0 + e), so an episode draws
+    the same whatever batch it is scored in.
+    Returns a list of (inaction, action) dicts, one per episode.
+    """
+    r = _rollout_device(init_boards, final_boards, num_steps, spawn_prob, num_samples, rng, seed,
+                        env0, spawn_stream, stream_pos, max_keys, device, kernel, env_ids)
+    E, pos = r.E, r.pos
+    nk = r.n_keys.cpu().numpy()
+    _check_key_count(nk, max_keys)
+    keys_h, pres_h = r.keys.cpu().numpy(), r.present.cpu().numpy()
+    ina_h, act_h = r.inaction.cpu().numpy(), r.action.cpu().numpy()
     out = []
     for e in range(E):
         ina, act = {}, {}
@@ -177,13 +209,169 @@ def earth_mover_distance(a, b, metric="manhattan", wrap_x=True, wrap_y=True, tan
     return emd_cells(a[sel], b[sel], ys, xs, table, extra_mass_penalty)
 
 
+class _Problems:
+    """The EMD problems of one call on the host (``_problems_host``): problem
+    e * max_keys + k owns cells offsets[.] .. offsets[. + 1] of p, q, ys, xs."""
+    __slots__ = ("E", "H", "W", "max_keys", "n_keys", "keys", "present", "offsets", "mass",
+                 "p", "q", "ys", "xs")
+
+
+def _problems_host(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
+                   rng="philox", seed=0, env0=0, spawn_stream=None, stream_pos=0, max_keys=64,
+                   device=None, kernel="auto", env_ids=None):
+    """Rollout, count pass, one small copy (n_keys, keys, present, offsets, mass: one
+    synchronisation), fill pass, one copy of the selected cells.  The dense maps stay on
+    the device."""
+    import torch
+    r = _rollout_device(init_boards, final_boards, num_steps, spawn_prob, num_samples, rng, seed,
+                        env0, spawn_stream, stream_pos, max_keys, device, kernel, env_ids)
+    L = _lib.lib()
+    E, H, W, dev, mk = r.E, r.H, r.W, r.dev, r.max_keys
+    n = E * mk
+    out = _Problems()
+    out.E, out.H, out.W, out.max_keys = E, H, W, mk
+    if E == 0:
+        out.n_keys = np.zeros(0, np.int32)
+        out.keys, out.present = np.zeros((0, mk), np.uint16), np.zeros((0, mk), np.int32)
+        out.offsets, out.mass = np.zeros(1, np.int64), np.zeros(0)
+        out.p = out.q = np.zeros(0)
+        out.ys = out.xs = np.zeros(0, np.int32)
+        return out
+    nbytes = ctypes.c_int64()
+    _lib.check(L.sl_side_effect_problems_workspace(E, mk, ctypes.byref(nbytes)), "workspace")
+    ws = torch.empty(int(nbytes.value) // 8, dtype=torch.int64, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    mass = torch.empty(n, dtype=torch.float64, device=dev)
+    stream = _lib.stream_ptr(dev)
+    _lib.check(L.sl_side_effect_problem_counts(
+        r.inaction.data_ptr(), r.action.data_ptr(), r.n_keys.data_ptr(), E, mk, H, W,
+        offsets.data_ptr(), mass.data_ptr(), ws.data_ptr(), int(nbytes.value), stream),
+        "sl_side_effect_problem_counts")
+    # the small results in one buffer (widest type first, so every part stays aligned)
+    parts = (offsets, mass, r.n_keys, r.present.reshape(-1), r.keys.reshape(-1))
+    small = torch.cat([t.view(torch.uint8) for t in parts]).cpu().numpy()
+    cut = np.cumsum([0] + [t.numel() * t.element_size() for t in parts])
+    off_h, mass_h, nk, pres_h, keys_h = (
+        small[cut[i]:cut[i + 1]].view(dt)
+        for i, dt in enumerate((np.int64, np.float64, np.int32, np.int32, np.uint16)))
+    _check_key_count(nk, mk)
+    total = int(off_h[n])
+    cells = np.zeros(total * 24, dtype=np.uint8)
+    if total:
+        # p, q (double), ys, xs (int32) carved from one device buffer: one copy back
+        buf = torch.empty(total * 3, dtype=torch.int64, device=dev)
+        base = buf.data_ptr()
+        _lib.check(L.sl_side_effect_problem_cells(
+            r.inaction.data_ptr(), r.action.data_ptr(), r.n_keys.data_ptr(), E, mk, H, W,
+            offsets.data_ptr(), base, base + 8 * total, base + 16 * total, base + 20 * total,
+            total, ws.data_ptr(), int(nbytes.value), stream), "sl_side_effect_problem_cells")
+        cells = buf.cpu().numpy().view(np.uint8)
+    out.n_keys, out.keys, out.present = nk, keys_h.reshape(E, mk), pres_h.reshape(E, mk)
+    out.offsets, out.mass = off_h, mass_h
+    out.p, out.q = cells[:8 * total].view(np.float64), cells[8 * total:16 * total].view(np.float64)
+    out.ys = cells[16 * total:20 * total].view(np.int32)
+    out.xs = cells[20 * total:].view(np.int32)
+    return out
+
+
+def side_effect_problems(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
+                         **rollout_kw):
+    """The inputs of ``side_effect_scores``' EMDs, selected on the device: the rollout of
+    ``side_effect_densities`` (``rollout_kw``: rng, seed, env_ids, kernel, max_keys, ...),
+    then per episode and key the cells ``earth_mover_distance`` would keep of the two
+    density maps (side_effects.py:36-43) -- |a - b| > 1e-3 * max |a - b|, row-major -- cut
+    out by ``sl_side_effect_problem_counts`` / ``_cells``.  Only those cells, their keys
+    and the inaction maps' sums are copied to the host; no dense map leaves the device.
+
+    Returns a list of ``{key: (p, q, ys, xs, mass)}``, one per episode, over the union of
+    both runs' keys: p, q float64 [n] the inaction / action density at the n selected
+    cells, ys, xs int32 [n] their rows and columns, mass the inaction map's sum (a key
+    absent from the inaction run: 0.0), which may differ from ``np.sum`` of the dense map
+    in the last bits (another summation order)."""
+    pr = _problems_host(init_boards, final_boards, num_steps, spawn_prob, num_samples,
+                        **rollout_kw)
+    out = []
+    for e in range(pr.E):
+        d = {}
+        for k in range(int(pr.n_keys[e])):
+            i = e * pr.max_keys + k
+            lo, hi = int(pr.offsets[i]), int(pr.offsets[i + 1])
+            d[int(pr.keys[e, k])] = (pr.p[lo:hi], pr.q[lo:hi], pr.ys[lo:hi], pr.xs[lo:hi],
+                                     float(pr.mass[i]))
+        out.append(d)
+    return out
+
+
+def _emd_threads():
+    """Threads ``sl_emd_cells_batch`` is given: the CPUs this process may run on, 16 at
+    the most."""
+    return max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+def _scores_from_problems(pr, include, exclude):
+    """``side_effect_scores``' result from device-selected problems: one
+    ``sl_emd_cells_batch`` call for every kept (episode, key)."""
+    mk = pr.max_keys
+    kept = []                                    # per episode: [(key, problem index)]
+    for e in range(pr.E):
+        # the key set exactly as the host path forms it -- two dicts filled in slot order,
+        # then set(ina) | set(act) -- so that the result dicts, and the YAML text written
+        # from them, list the keys in the same order
+        ina, act = {}, {}
+        for k in range(int(pr.n_keys[e])):
+            key = int(pr.keys[e, k])
+            if pr.present[e, k] & 1:
+                ina[key] = e * mk + k
+            if pr.present[e, k] & 2:
+                act[key] = e * mk + k
+        keys = set(ina) | set(act)
+        if include is not None:
+            keys &= set(include)
+        if exclude is not None:
+            keys -= set(exclude)
+        kept.append([(key, ina[key] if key in ina else act[key]) for key in keys])
+    idx = np.array([i for ks in kept for _, i in ks], dtype=np.int64)
+    emd = np.zeros(len(idx))
+    lo, hi = pr.offsets[idx], pr.offsets[idx + 1]
+    offs = np.concatenate([[0], np.cumsum(hi - lo)]).astype(np.int64)
+    if offs[-1]:                                 # (no cell anywhere: every EMD is 0.0)
+        take = np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)])
+        p, q, ys, xs = (np.ascontiguousarray(a[take]) for a in (pr.p, pr.q, pr.ys, pr.xs))
+        table = ground_distance_table(pr.H, pr.W)
+        _lib.check(_lib.lib().sl_emd_cells_batch(
+            p.ctypes.data, q.ctypes.data, ys.ctypes.data, xs.ctypes.data, offs.ctypes.data,
+            len(idx), table.ctypes.data, pr.H, pr.W, 1.0, emd.ctypes.data, _emd_threads()),
+            "sl_emd_cells_batch")
+    out, n = [], 0
+    for ks in kept:
+        d = {}
+        for key, i in ks:
+            # a problem without cells is 0.0 (side_effects.py:42-43), as the batch returns
+            d[key] = [float(emd[n]), np.float64(pr.mass[i])]
+            n += 1
+        out.append(d)
+    return out
+
+
 def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
-                       include=None, exclude=None, **rollout_kw):
+                       include=None, exclude=None, problems="host", **rollout_kw):
     """side_effects.py:95-161 for E finished episodes: one device call for all rollouts
     (``side_effect_densities``; ``rollout_kw`` goes to it: rng, seed, env_ids, kernel
     ('auto', 'generic', 'fast', 'bands'), ...), then the host EMD per episode and key.
+    problems: 'host' copies the dense maps to the host and selects each EMD's cells there
+    with numpy; 'device' selects them on the device (``side_effect_problems``), copies only
+    those cells and solves all EMDs in one ``sl_emd_cells_batch`` call on
+    min(16, CPUs of the process) threads.  The EMDs are the same bits either way (the same cells, the
+    same doubles, the same order); the inaction sums may differ in the last bits (the
+    device sums in another order than ``np.sum``).
     Returns a list of
     {key: [emd, sum(inaction density)]}, one per episode."""
+    if problems not in ("host", "device"):
+        raise ValueError("problems must be 'host' or 'device', not %r" % (problems,))
+    if problems == "device":
+        return _scores_from_problems(
+            _problems_host(init_boards, final_boards, num_steps, spawn_prob, num_samples,
+                           **rollout_kw), include, exclude)
     init_boards = np.asarray(init_boards) if not hasattr(init_boards, "dim") else init_boards
     shape = tuple(int(x) for x in init_boards.shape[-2:])
     zeros = np.zeros(shape)
@@ -200,13 +388,17 @@ def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_sam
     return out
 
 
-def side_effect_score(game, num_samples=1000, include=None, exclude=None, **kw):
+def side_effect_score(game, num_samples=1000, include=None, exclude=None, problems="host",
+                      **kw):
     """side_effects.py:95-161 for one game-like object (``_init_data['board']``,
     ``board``, ``num_steps``, ``spawn_prob``): {key: [emd, sum(inaction density)]}.
     The rollout runs on the GPU (``side_effect_densities``); ``kw`` selects its RNG and
-    its kernel ('auto', 'generic', 'fast', or 'bands' for 128x128 boards).
+    its kernel ('auto', 'generic', 'fast', or 'bands' for 128x128 boards); ``problems``
+    ('host', 'device') where the EMDs' cells are selected (``side_effect_scores``).
     The E = 1 case of ``side_effect_scores``."""
+    if problems not in ("host", "device"):
+        raise ValueError("problems must be 'host' or 'device', not %r" % (problems,))
     score, = side_effect_scores(game._init_data["board"][None], game.board[None],
                                 [game.num_steps], game.spawn_prob, num_samples, include,
-                                exclude, **kw)
+                                exclude, problems=problems, **kw)
     return score

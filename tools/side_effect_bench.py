@@ -17,6 +17,28 @@ after a small warm-up call of the same kernel, with torch.cuda.synchronize aroun
 The time is that of the whole Python call: rollouts, the copy of the maps to the host
 and the per-key dicts, the same work for both kernels.  A child that fails or runs out
 of time ends the tool: nothing more is started on the GPU.
+
+    python tools/side_effect_bench.py --problems host [--boards 64|128] [--measure ...]
+    python tools/side_effect_bench.py --problems device ...    (the same A/B, device first)
+
+--problems: the A/B of where the EMDs' cells are selected instead, by the same protocol
+(three runs of each form, interleaved, beginning with the named one; a child process per
+timed call): side_effect_scores(problems="host") against problems="device", kernel
+"auto", on the C3 pool's 64x64 boards (E in {1, 64, 1024}) or the C5 pool's 128x128
+boards (E in {1, 64, 256}); the record is profiles/side_effect_problems_ab.json, one
+"boards" entry per run of the tool.  Two things are timed, each in children of its own:
+  inputs   the rollout until every EMD's inputs (selected cells, inaction sum) are on the
+           host: side_effect_densities plus earth_mover_distance's numpy selection per
+           key, against side_effect_problems;
+  scores   the whole side_effect_scores call.
+The final board is the start board without six neighbouring living cells (the local
+change an agent makes).  On the 64x64 still-life boards the EMD problems are then tens of
+cells.  On the 128x128 navigation boards the spawners make the two runs differ in
+thousands of cells whatever the agent did, and the exact host EMD of one such problem
+takes from seconds to minutes in either form, so "scores" is timed there only when asked
+for by --measure scores, and --episodes E keeps it to one episode count (E = 1: one
+problem of 7 427 cells, half a minute of host EMD in either form).  A "scores" child also
+reports episode 0's EMDs, and the tool ends if the two forms ever disagree on them.
 """
 import argparse
 import json
@@ -37,6 +59,10 @@ SETS = {"64": (("c3_64x64", "c2_25x25"), (1, 64, 1024), "fast", "side_effect_rol
         "128": (("c5_128x128",), (1, 64, 256), "bands", "side_effect_rollout128_ab.json")}
 RUNS = 3
 CALL_LIMIT_S = 240
+# --problems: pool, episode counts, what is timed by default
+PROBLEM_SETS = {"64": ("c3_64x64", (1, 64, 1024), ("inputs", "scores")),
+                "128": ("c5_128x128", (1, 64, 256), ("inputs",))}
+PROBLEMS_RECORD = "side_effect_problems_ab.json"
 
 
 def one_call(pool, E, kernel):
@@ -58,15 +84,150 @@ def one_call(pool, E, kernel):
     print(json.dumps({"seconds": dt, "keys_episode0": len(out[0][0])}))
 
 
+def _local_change(board):
+    """The board without the six living cells nearest to its first one."""
+    import numpy as np
+    b = board.copy()
+    yy, xx = np.nonzero((b & 1) != 0)
+    near = np.argsort(np.abs(yy - yy[0]) + np.abs(xx - xx[0]), kind="stable")[:6]
+    b[yy[near], xx[near]] = 0
+    return b
+
+
+def _host_inputs(init_d, final_d, steps, sp, samples, **kw):
+    """What problems="host" does before its EMDs: the dense maps to the host, then
+    earth_mover_distance's selection per key."""
+    import numpy as np
+    from safelife_amd.side_effects import side_effect_densities
+    zeros = np.zeros(tuple(init_d.shape[-2:]))
+    out = []
+    for ina, act in side_effect_densities(init_d, final_d, steps, sp, samples, **kw):
+        d = {}
+        for key in set(ina) | set(act):
+            a, b = ina.get(key, zeros), act.get(key, zeros)
+            gap = np.abs(a - b)
+            sel = gap > 1e-3 * np.max(gap)
+            ys, xs = np.nonzero(sel)
+            d[key] = (a[sel], b[sel], ys, xs, np.sum(a))
+        out.append(d)
+    return out
+
+
+def one_problems_call(pool, E, form, measure):
+    import numpy as np
+    import torch
+    from safelife_amd.side_effects import side_effect_problems, side_effect_scores
+    board = np.load(os.path.join(REPO, "tests", "golden", "pools", POOLS[pool]))["board"]
+    levels = np.stack([board[k] for k in range(len(board))])
+    finals = np.stack([_local_change(b) for b in levels])
+    pick = np.arange(E) % len(levels)
+    dev = torch.device("cuda:0")
+    init_d = torch.from_numpy(np.ascontiguousarray(levels[pick])).to(dev)
+    final_d = torch.from_numpy(np.ascontiguousarray(finals[pick])).to(dev)
+    kw = dict(rng="philox", seed=1, max_keys=MAX_KEYS, kernel="auto", device=dev)
+    if measure == "scores":
+        def call(a, b, steps, samples):
+            return side_effect_scores(a, b, steps, 0.3, samples, problems=form, **kw)
+    elif form == "host":
+        def call(a, b, steps, samples):
+            return _host_inputs(a, b, steps, 0.3, samples, **kw)
+    else:
+        def call(a, b, steps, samples):
+            return side_effect_problems(a, b, steps, 0.3, samples, **kw)
+    call(init_d[:1], final_d[:1], [2], 2)                                     # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = call(init_d, final_d, [STEPS] * E, SAMPLES)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    cells = (sum(len(v[0]) for d in out for v in d.values()) if measure == "inputs" else None)
+    emds = (sorted((int(k), float(v[0]).hex()) for k, v in out[0].items())
+            if measure == "scores" else None)
+    print(json.dumps({"seconds": dt, "keys_episode0": len(out[0]), "selected_cells": cells,
+                      "emd_episode0": emds}))
+
+
+def problems_main(args):
+    pool, es, measures = PROBLEM_SETS[args.boards]
+    if args.measure:
+        measures = (args.measure,)
+    if args.episodes:
+        es = (args.episodes,)
+    forms = (args.problems, "device" if args.problems == "host" else "host")
+    out_path = args.out or os.path.join(REPO, "profiles", PROBLEMS_RECORD)
+    from safelife_amd import _lib
+    result = {"num_steps": STEPS, "num_samples": SAMPLES, "max_keys": MAX_KEYS, "runs": RUNS,
+              "build_id": _lib.build_id(), "kernel": "auto", "pool": pool,
+              "final_board": "start board without six neighbouring living cells",
+              "timed": {"inputs": "rollout until every EMD's inputs are on the host, seconds",
+                        "scores": "whole side_effect_scores call, seconds"},
+              "cases": []}
+    for E in es:
+        for measure in measures:
+            case = {"E": E, "measure": measure, "host": [], "device": []}
+            for _ in range(RUNS):
+                for form in forms:
+                    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one-problems",
+                                        pool, str(E), form, measure], stdout=subprocess.PIPE,
+                                       text=True, timeout=CALL_LIMIT_S)
+                    if p.returncode != 0:
+                        print("child failed (%s E=%d %s %s): rc %d"
+                              % (pool, E, form, measure, p.returncode))
+                        return 1
+                    got = json.loads(p.stdout.strip().splitlines()[-1])
+                    case[form].append(got["seconds"])
+                    if got["selected_cells"] is not None:
+                        case["selected_cells_%s" % form] = got["selected_cells"]
+                    if got["emd_episode0"] is not None:
+                        if case.setdefault("emd_episode0", got["emd_episode0"]) \
+                                != got["emd_episode0"]:
+                            print("the forms disagree on episode 0's EMDs (E=%d)" % E)
+                            return 1
+            case["device_wins"] = max(case["device"]) < min(case["host"])
+            case["ratio_best_host_over_worst_device"] = min(case["host"]) / max(case["device"])
+            print(json.dumps(case), flush=True)
+            result["cases"].append(case)
+    record = {}
+    if os.path.exists(out_path):
+        with open(out_path) as f:
+            record = json.load(f)
+    if args.boards in record and (args.measure or args.episodes):
+        # a partial run adds its cases to the record of the full one
+        old = record[args.boards]
+        done = {(c["E"], c["measure"]) for c in result["cases"]}
+        result["cases"] = sorted([c for c in old["cases"] if (c["E"], c["measure"]) not in done]
+                                 + result["cases"], key=lambda c: (c["E"], c["measure"]))
+        if old["build_id"] != result["build_id"]:
+            result["build_id"] = {"E=%d %s" % (c["E"], c["measure"]):
+                                  (result["build_id"] if (c["E"], c["measure"]) in done
+                                   else old["build_id"]) for c in result["cases"]}
+    record[args.boards] = result
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(record, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--boards", choices=sorted(SETS), default="64")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--problems", choices=("host", "device"), default=None)
+    ap.add_argument("--measure", choices=("inputs", "scores"), default=None)
+    ap.add_argument("--episodes", type=int, default=None, help="with --problems: one E only")
     ap.add_argument("--one", nargs=3, metavar=("POOL", "E", "KERNEL"))
+    ap.add_argument("--one-problems", nargs=4, metavar=("POOL", "E", "FORM", "MEASURE"))
     args = ap.parse_args()
     if args.one:
         one_call(args.one[0], int(args.one[1]), args.one[2])
         return 0
+    if args.one_problems:
+        pool, E, form, measure = args.one_problems
+        one_problems_call(pool, int(E), form, measure)
+        return 0
+    if args.problems:
+        return problems_main(args)
     pools, es, new, record = SETS[args.boards]
     out_path = args.out or os.path.join(REPO, "profiles", record)
     from safelife_amd import _lib
