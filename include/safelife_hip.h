@@ -718,6 +718,10 @@ typedef struct sl_env_cfg {
                                        *stream_pos on with no host buffer      */
     int32_t board_mode;             /* SL_BOARD_*: where a 128x128 step leaves the
                                        board (sl_env_state.board_planes)       */
+    int32_t planes64_waves;         /* 64x64 plane mode, C3 / C4 planes, gray goals,
+                                       no views: 0 or 6, the kernel sized for six
+                                       waves per SIMD; 5, its five-wave twin (same
+                                       results; kept for comparison)           */
 } sl_env_cfg;
 
 /*

@@ -546,12 +546,14 @@ __device__ __forceinline__ u32 colour_in(u32 c0, u32 c1, u32 c2, int s) {
 // them there when the board's own bits 12-14 are all clear, so those bits count as 0
 // in the side-effect compare; white goals may be cleared: rows black and white of the
 // point table are equal, and neither counts as possible); gc is then not read.
-template <bool GC_IN_B = false>
+// [W0, W1): the words summed (both; the six-wave plane kernel sums one word at a time, so
+// that only that word's start planes are live: sl_planes64_step.inc).
+template <bool GC_IN_B = false, int W0 = 0, int W1 = 2>
 __device__ __forceinline__ void score_planes(const u32 B[32], const u32 gc[3][2], const u32 S[32],
                                              int *pts, int *scr, int *pos, int *side) {
     int p = 0, q = 0, r = 0, e = 0;
 #pragma unroll
-    for (int w = 0; w < 2; w++) {
+    for (int w = W0; w < W1; w++) {
         const u32 c0 = PL(B, 9, w), c1 = PL(B, 10, w), c2 = PL(B, 11, w);
         const u32 g0 = GC_IN_B ? PL(B, 12, w) : gc[0][w];
         const u32 g1 = GC_IN_B ? PL(B, 13, w) : gc[1][w];

@@ -83,7 +83,26 @@ __device__ __forceinline__ void read_pairs(const lds_u32 *buf, int lane, u32 D[3
 // life; held in registers instead, it spills).
 // KEEP: the planes any board (and so any start board) can hold; a row whose two planes
 // the scores do not need (1, 3, 6 are never read) or no board holds is not copied
-template <u32 KEEP = 0xFFFFu>
+// PACK: the copied rows lie one after the other in LDS (the six-wave kernel's 6 KiB
+// buffer: KEEP 0x877F copies 5 of the 7 rows, 5 KiB), not each in its own slot
+constexpr int pool_row_plane(int k) { return k < 2 ? 2 * k : 2 * k + 2; }   // row k: planes p0, p0 + 1
+constexpr bool pool_row_copied(u32 keep, int k) {
+    return (((keep & 0xFF85u) >> pool_row_plane(k)) & 3u) != 0u;             // planes 0, 2, 7-15
+}
+constexpr int pool_row_slot(u32 keep, bool pack, int k) {
+    if (!pack) return k;
+    int n = 0;
+    for (int i = 0; i < k; i++) n += pool_row_copied(keep, i) ? 1 : 0;
+    return n;
+}
+// dwords of LDS the copied rows take
+constexpr int pool_rows_dwords(u32 keep, bool pack) {
+    int top = 0;
+    for (int k = 0; k < 7; k++)
+        if (pool_row_copied(keep, k)) top = pool_row_slot(keep, pack, k) + 1;
+    return top * 256;
+}
+template <u32 KEEP = 0xFFFFu, bool PACK = false>
 __device__ __forceinline__ void pool_dma(const sl_level_pool &pool, int li, lds_u32 *buf,
                                          int lane) {
     const char *pl = reinterpret_cast<const char *>(pool.board_planes + (int64_t)li * 16 * N);
@@ -92,8 +111,9 @@ __device__ __forceinline__ void pool_dma(const sl_level_pool &pool, int li, lds_
     for (int k = 0; k < 7; k++) {       // LDS row k <- planes (0,1), (2,3), (6,7) .. (14,15)
         const int p0 = k < 2 ? 2 * k : 2 * k + 2;
         if (!((need >> p0) & 3u)) continue;
+        const int slot = PACK ? pool_row_slot(KEEP, true, k) : k;
         __builtin_amdgcn_global_load_lds((const void *)(pl + p0 * N * 8 + lane * 16),
-                                         (__attribute__((address_space(3))) void *)(buf + k * 256),
+                                         (__attribute__((address_space(3))) void *)(buf + slot * 256),
                                          16, 0, 0);
     }
 }
@@ -119,6 +139,62 @@ __device__ __forceinline__ void pool_planes_lds(const lds_u32 *buf, int dy, int 
         PL(S, p, 1) = lo_first ? __builtin_amdgcn_alignbit(b1, b0, sh)
                                : __builtin_amdgcn_alignbit(b0, b1, sh);
     }
+}
+// The same from pool_dma<KEEP, true>'s packed rows, for the column word W alone (the
+// other word of S is left as it is): the six-wave kernel scores one word at a time.
+template <u32 KEEP, int W>
+__device__ __forceinline__ void pool_planes_lds_word(const lds_u32 *buf, int dy, int dx,
+                                                     int lane, u32 S[32]) {
+    const int c = (2 * (lane >> 1) + W - dx) & 63;
+    const int r = (32 * (lane & 1) - dy) & 63;
+    const bool lo_first = r < 32;
+    const u32 sh = (u32)(r & 31);
+#pragma unroll
+    for (int p = 0; p < 16; p++) {
+        if (p == 1 || (p >= 3 && p <= 6) || !((KEEP >> p) & 1u)) {
+            PL(S, p, W) = 0u;
+            continue;
+        }
+        const int row = p < 4 ? p >> 1 : (p >> 1) - 1;                  // pool_dma's row k
+        const int slot = 2 * pool_row_slot(KEEP, true, row) + (p & 1);  // LDS plane slot
+        const lds_u32 *q = buf + slot * 128;            // 64 columns x 2 dwords
+        const u32 a0 = q[2 * c], a1 = q[2 * c + 1];
+        PL(S, p, W) = lo_first ? __builtin_amdgcn_alignbit(a1, a0, sh)
+                               : __builtin_amdgcn_alignbit(a0, a1, sh);
+    }
+}
+
+// A uint16 board through a buffer of 4 KiB (the six-wave kernel's): two passes of 32 rows,
+// each DMA'd to the start of the buffer (row-major, no rotation: within a half the 32
+// lanes that read it take 32 consecutive dwords of each row) and read by the lanes of
+// that half -- read_pairs' dwords.  A DMA's data is waited for (vmcnt) before it is read,
+// and a half's reads are retired (lgkmcnt) before the next DMA overwrites it, the
+// caller's earlier reads of the buffer included.
+__device__ __forceinline__ void board_pairs_halves(const uint16_t *__restrict__ src, lds_u32 *buf,
+                                                   int lane, u32 D[32]) {
+    const int h = lane & 1, j = lane >> 1;
+    // the lane's source offset, computed here: shared with the kernel's first DMAs it is
+    // held from there through the rule, and at 80 registers spilled round the draw loop
+    int l16 = lane * 16;
+    asm volatile("" : "+v"(l16));
+    const char *s = reinterpret_cast<const char *>(src) + l16;
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        wait_lgkm();
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < 4; k++)        // 4 x (64 lanes x 16 B): rows 32 half + 8k .. + 7
+            __builtin_amdgcn_global_load_lds((const void *)(s + half * 4096 + k * 1024),
+                                             (__attribute__((address_space(3))) void *)(buf + k * 256),
+                                             16, 0, 2);
+        wait_vm();
+        if (h == half) {
+#pragma unroll
+            for (int y = 0; y < 32; y++) D[y] = buf[y * 32 + j];
+        }
+    }
+    wait_lgkm();
 }
 
 
@@ -911,7 +987,7 @@ __global__ void __launch_bounds__(64, planes_min_waves(K16, OBS))
 k_env_step_bits64_planes(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     uint16_t *const vm = nullptr;
-    constexpr bool GRAY = false;
+    constexpr bool GRAY = false, W6 = false;
 #include "sl_planes64_step.inc"
 }
 
@@ -927,7 +1003,27 @@ k_env_planes64_gray(StepKArgs ka) {
     static_assert(OBS <= 1, "channel views load the three colour planes");
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     uint16_t *const vm = nullptr;
-    constexpr bool GRAY = true;
+    constexpr bool GRAY = true, W6 = false;
+#include "sl_planes64_step.inc"
+}
+
+// k_env_planes64_gray<K16, 0> at six waves per SIMD: at most 80 VGPRs and a buffer of
+// 6 KiB (24 waves x 6 KiB = 144 of the CU's 160 KiB).  The buffer holds the 4 KiB of stored
+// plane words, then the 5 KiB of start-plane rows the scores need, packed; the two cold
+// entries that stage a whole uint16 board (the step after a reset or a host write, and a
+// caller-written start board) take it in two halves (board_pairs_halves).  Same loads,
+// same stores, same results.  Only the C3 / C4 planes are instantiated.  (Named apart
+// from k_env_step_* and k_env_planes64_gray, whose resource tests count by name;
+// tests/test_kernel_resources_w6.py.)
+constexpr int kMinWavesW6 = 6;
+constexpr int kStageDwW6 = 1536;
+template <u32 K16>
+__global__ void __launch_bounds__(64, kMinWavesW6)
+k_env_planes64_w6(StepKArgs ka) {
+    __shared__ __attribute__((aligned(16))) u32 stage[kStageDwW6];
+    uint16_t *const vm = nullptr;
+    constexpr int OBS = 0;
+    constexpr bool GRAY = true, W6 = true;
 #include "sl_planes64_step.inc"
 }
 
@@ -943,7 +1039,7 @@ k_env_planes64_chan(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     __shared__ __attribute__((aligned(16))) uint16_t vmask[sl::obs::kFusedChanCells];
     uint16_t *const vm = vmask;
-    constexpr bool GRAY = false;
+    constexpr bool GRAY = false, W6 = false;
 #include "sl_planes64_step.inc"
 }
 
@@ -1120,7 +1216,8 @@ int sync_board_planes64(const sl_env_state &st, int demote, hipStream_t s) {
 
 int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
                      const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                     uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s) {
+                     uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s,
+                     int planes64_waves) {
     if (st.H != N || st.W != N) return SL_ETOOBIG;
     const unsigned grid = (unsigned)st.B;
     const StepKArgs ka{st, a, fx, actions, ctp, ctc, reward, done, flags, ep_len, ep_rew};
@@ -1151,8 +1248,10 @@ int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra 
                 // goals all black or white: the instances that skip their colours
                 if (kind)
                     hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 1>), dim3(grid), dim3(64), 0, s, ka);
-                else
+                else if (planes64_waves == 5)  // (sl_env_cfg.planes64_waves: the five-wave twin)
                     hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 0>), dim3(grid), dim3(64), 0, s, ka);
+                else
+                    hipLaunchKernelGGL((k_env_planes64_w6<kKeepC3>), dim3(grid), dim3(64), 0, s, ka);
             } else if (fx.obs_out) {
                 if (keep == kKeepC3Fixed)
                     hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepC3, 1>), dim3(grid), dim3(64), 0, s, ka);

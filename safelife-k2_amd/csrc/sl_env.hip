@@ -1057,6 +1057,8 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
     // completes (and demotes) it.  (Replay: with draw planes, the decided form.)
     const bool planes128 = st->board_planes && st->planes_ok && st->H == 128 && st->W == 128;
     if (cfg->board_mode != SL_BOARD_AUTO && cfg->board_mode != SL_BOARD_UINT16) return SL_EINVAL;
+    if (cfg->planes64_waves != 0 && cfg->planes64_waves != 5 && cfg->planes64_waves != 6)
+        return SL_EINVAL;
     const bool fuse_obs128 = fast128 && planes128 && cfg->obs_out && !cap &&
                              cfg->board_mode != SL_BOARD_UINT16 &&
                              (!replay || st->elig_planes) && oa.mode == SL_OBS_PACKED &&
@@ -1113,7 +1115,7 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
     } else if (fast) {
         int rc = launch_step_bits(*st, a, fx, actions, cfg->can_toggle_powers,
                                   cfg->can_toggle_colors, reward, done, info_flags, ep_len,
-                                  ep_reward, s);
+                                  ep_reward, s, cfg->planes64_waves);
         if (rc || cfg->stream_phase == 1) return rc;
         reset_done = fx.fuse_reset && fx.pool.K > 0;
     } else {

@@ -405,6 +405,7 @@ constexpr int kViewMaxRows128 = 96;
 // bit-sliced 64x64 kernel (sl_bits.hip)
 int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
                      const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                     uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s);
+                     uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s,
+                     int planes64_waves = 0);   // sl_env_cfg.planes64_waves
 
 }  // namespace sl

@@ -10,7 +10,10 @@
 // (k_env_planes64_gray's: sl_env_state.goals_gray holds, every goal cell black or white --
 // the scores read no goal colour, the packed views one plane; OBS <= 1), the kernel's
 // argument `StepKArgs ka`, the wave's buffer `u32 stage[N * N / 2]` in LDS, and `vm`, the
-// view's channel masks in LDS (uint16_t[kFusedChanCells]; unused when OBS < 2).
+// view's channel masks in LDS (uint16_t[kFusedChanCells]; unused when OBS < 2), and the
+// constant W6 (k_env_planes64_w6's: `stage` is 6 KiB, not 8 -- the pool's start-plane rows
+// are packed, a uint16 board is staged in two passes of 32 rows, and the scores read the
+// start planes one column word at a time; OBS == 0).
 // With views, the goal colours are added into planes 12-14 (a bit-sliced adder, exact
 // whatever the board's bits), ONE transpose puts the view-form rows into the buffer.
     const sl_env_state &st = ka.st;
@@ -20,6 +23,15 @@
     const int lane = threadIdx.x;
     lds_u32 *buf = (lds_u32 *)&stage[0];
     const PlaneSlots<K16> ps = PlaneSlots<K16>::of(st.board_zero, st.agent_planes);
+    // what the buffer holds at one time: the stored plane words, the pool's start-plane
+    // rows, or (W6) half a uint16 board
+    constexpr int kStageDw = (int)(sizeof(stage) / sizeof(u32));
+    static_assert(!W6 || (PlaneSlots<K16>::kFixed && OBS == 0), "W6: fixed planes, no views");
+    static_assert(!W6 || 2 * __builtin_popcount(K16 & ~kAgentC3 & 0xFFFFu) * 64 <= kStageDw,
+                  "the stored plane words fit the buffer");
+    static_assert(pool_rows_dwords(K16 ? K16 : 0xFFFFu, W6) <= kStageDw,
+                  "the pool's start-plane rows fit the buffer");
+    static_assert(kStageDw >= (W6 ? N * N / 4 : N * N / 2), "a board, or half of one (W6)");
     Pre pre;
     // GRAY: no colour plane for the scores (rows black and white of the point table are
     // equal, neither counts as possible or as a blue goal: they score as black, 0); the
@@ -64,10 +76,13 @@
     if (!pin) {
         // a step into plane mode: the uint16 board instead, transposed and put into the
         // buffer in the planes' layout, so everything below reads planes
-        dma_board(st.board + off, buf, lane);
-        wait_vm();
+        if (!W6) {
+            dma_board(st.board + off, buf, lane);
+            wait_vm();
+        }
         u32 R[32];
-        read_pairs(buf, lane, R);
+        if (W6) board_pairs_halves(st.board + off, buf, lane, R);
+        else read_pairs(buf, lane, R);
         transpose32(R);
 #pragma unroll
         for (int q = 0; q < 32; q++)
@@ -123,8 +138,10 @@
     for (int q = 0; q < 32; q++) PB[q] = ps.stored(q) ? buf[ps.pos(q) * 64 + lane] : 0u;
     wait_lgkm();
     constexpr u32 KEEP = K16 ? K16 : 0xFFFFu;
-    if (roll < 0) dma_board(st.start_board + off, buf, lane);
-    else pool_dma<KEEP>(fx.pool, rec(V, R_LI), buf, lane);
+    // (W6: a caller-written start board is staged in two passes where it is read, below)
+    if (roll < 0) {
+        if (!W6) dma_board(st.start_board + off, buf, lane);
+    } else pool_dma<KEEP, W6>(fx.pool, rec(V, R_LI), buf, lane);
     (void)mux_edits(PB, ne, eidx, eval, lane);
     // the agent planes: one word pair, the bit of the agent's cell after the action (the
     // rule changes no such cell: the host puts a plane in agent_planes only where the
@@ -152,9 +169,10 @@
     u32 PS[32];
     wait_vm();
     if (roll >= 0) {
-        pool_planes_lds<KEEP>(buf, roll >> 16, roll & 0xFFFF, lane, PS);
+        if (!W6) pool_planes_lds<KEEP>(buf, roll >> 16, roll & 0xFFFF, lane, PS);
     } else {
-        read_pairs(buf, lane, PS);
+        if (W6) board_pairs_halves(st.start_board + off, buf, lane, PS);
+        else read_pairs(buf, lane, PS);
         transpose32(PS);
         // planes no board holds: no start board either (as pool_planes_lds has them), so
         // neither path keeps a register for them
@@ -164,6 +182,22 @@
     }
     int pts, scr, pos, side;
     const u32 gblack[3][2] = {{0u, 0u}, {0u, 0u}, {0u, 0u}};
+    if (W6 && roll >= 0) {
+        // one column word at a time: that word's start planes are read from LDS and
+        // scored before the other's are read, so half of them are live at once (read
+        // together, they are where this instance's register peak was)
+        const int dy = roll >> 16, dx = roll & 0xFFFF;
+        int p1, s1, o1, e1;
+        pool_planes_lds_word<KEEP, 0>(buf, dy, dx, lane, PS);
+        score_planes<false, 0, 1>(PB, GRAY ? gblack : gcol, PS, &pts, &scr, &pos, &side);
+        __builtin_amdgcn_sched_barrier(0);
+        pool_planes_lds_word<KEEP, 1>(buf, dy, dx, lane, PS);
+        score_planes<false, 1, 2>(PB, GRAY ? gblack : gcol, PS, &p1, &s1, &o1, &e1);
+        pts += p1;
+        scr += s1;
+        pos += o1;
+        side += e1;
+    } else
     score_planes(PB, GRAY ? gblack : gcol, PS, &pts, &scr, &pos, &side);
     const ScoreTotals tot = score_totals(pts, scr, pos, side);
     __builtin_amdgcn_sched_barrier(0);

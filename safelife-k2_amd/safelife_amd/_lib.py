@@ -74,7 +74,7 @@ class EnvCfg(ctypes.Structure):
                 ("obs_out", vp), ("obs_mode", i32), ("obs_vh", i32), ("obs_vw", i32),
                 ("obs_remove_white", i32), ("obs_nch", i32), ("obs_channels", i32 * 16),
                 ("capture", vp), ("stream_phase", i32), ("stream_base", vp), ("mt", vp),
-                ("board_mode", i32)]
+                ("board_mode", i32), ("planes64_waves", i32)]
 
 
 class MT19937(ctypes.Structure):

@@ -127,7 +127,7 @@ class SafeLifeVecEnv:
                  level_order="sequential", augment_roll=False, env0=0, n_total_envs=None,
                  can_toggle_powers=False, can_toggle_colors=False, obs_dtype="uint16",
                  compute_obs=True, global_counter=None, kernel="auto", stream_exchange=None,
-                 stream_ring="auto", board_mode="auto"):
+                 stream_ring="auto", board_mode="auto", planes64_waves=6):
         import torch
         self.torch = torch
         self.device = _lib.require_device(device)
@@ -178,6 +178,12 @@ class SafeLifeVecEnv:
         if board_mode not in ("auto", "planes", "uint16"):
             raise ValueError("board_mode must be 'auto', 'planes' or 'uint16'")
         self.board_mode = board_mode
+        # the 64x64 plane kernel of a C3 / C4 batch with gray goals and no views
+        # (sl_env_cfg.planes64_waves): 6, the kernel sized for six waves per SIMD, or 5,
+        # its five-wave twin -- same results, kept for comparison
+        if planes64_waves not in (5, 6):
+            raise ValueError("planes64_waves must be 5 or 6")
+        self.planes64_waves = planes64_waves
         self._board_read_at = None   # step index of the last `board` read
         self._step_index = 0
         # step index and auto_reset flag of the last launched step: the 64x64 and
@@ -567,6 +573,7 @@ class SafeLifeVecEnv:
         c.augment_roll = int(self.augment_roll)
         c.kernel = self.kernel
         c.board_mode = _lib.SL_BOARD_UINT16 if self._wants_uint16_board() else _lib.SL_BOARD_AUTO
+        c.planes64_waves = self.planes64_waves
         return c
 
     BOARD_READ_WINDOW = 4
