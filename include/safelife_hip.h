@@ -373,6 +373,37 @@ int sl_side_effect_problem_cells(const double *inaction, const double *action,
 int sl_emd_cells_batch(const double *p, const double *q, const int32_t *ys, const int32_t *xs,
                        const int64_t *offsets, int64_t nprob, const double *cost_table,
                        int H, int W, double extra_mass_penalty, double *out, int nthreads);
+/*
+ * The same distances solved on the device (k_emd_cells, sl_emd_device.hip: one wave per
+ * problem): what pyemd.emd returns at the reference's side_effects.py:56 for each
+ * problem's cells, bit for bit what sl_emd_cells returns for them -- the same IEEE
+ * double operations in the same order around an integer transport problem whose optimum
+ * does not depend on the method.  All pointers are device pointers: p, q, ys, xs and
+ * offsets (int64 [nprob + 1]) as sl_side_effect_problem_cells leaves them, cost_table
+ * double [2H-1][2W-1], out double [nprob], status int32 [nprob].
+ *   status[i] >= 0  solved: out[i] is the distance and status[i] the number of simplex
+ *                   pivots it took (0 also for a problem without cells, out[i] = 0.0,
+ *                   and for the cases decided without a transport)
+ *   status[i] <  0  not solved, out[i] = 0.0:
+ *     SL_EMD_ST_BADCELL  a cell off the board (sl_emd_cells: SL_EINVAL); checked before
+ *                        any table read
+ *     SL_EMD_ST_TOOBIG   more than SL_EMD_DEVICE_MAX_CELLS cells (or a negative count):
+ *                        not attempted; the limit is what one wave's share of LDS holds
+ *                        (14 656 B per problem)
+ *     SL_EMD_ST_PIVOTS   the pivot cap (a fixed multiple of the transport's node count)
+ *                        ran out, or a consistency check of the tree failed
+ *   A caller solves the TOOBIG and PIVOTS problems with sl_emd_cells_batch.
+ * nprob == 0 is SL_OK without a launch; nprob < 0, H or W < 1 or > 32768, nprob > 2^31 - 1
+ * or a null pointer with nprob > 0 is SL_EINVAL before any launch.
+ */
+#define SL_EMD_DEVICE_MAX_CELLS 256
+#define SL_EMD_ST_BADCELL (-1)
+#define SL_EMD_ST_TOOBIG (-2)
+#define SL_EMD_ST_PIVOTS (-3)
+int sl_emd_cells_device(const double *p, const double *q, const int32_t *ys, const int32_t *xs,
+                        const int64_t *offsets, int64_t nprob, const double *cost_table,
+                        int H, int W, double extra_mass_penalty, double *out, int32_t *status,
+                        void *stream);
 
 /* ------------------------------------------------------------------ envs -- */
 

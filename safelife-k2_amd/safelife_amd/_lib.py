@@ -17,6 +17,9 @@ SL_RNG_STREAM, SL_RNG_PHILOX = 0, 1
 SL_KERNEL_AUTO, SL_KERNEL_GENERIC, SL_KERNEL_FAST = 0, 1, 2
 SL_KERNEL_BANDS = 3     # sl_side_effect_densities_k only: the 128x128 four-wave rollout
 SL_STREAM_ERR_RANGE, SL_STREAM_ERR_THRESHOLD = 1, 2
+# sl_emd_cells_device: the size limit of a problem and the negative status codes
+SL_EMD_DEVICE_MAX_CELLS = 256
+SL_EMD_ST_BADCELL, SL_EMD_ST_TOOBIG, SL_EMD_ST_PIVOTS = -1, -2, -3
 SL_BOARD_AUTO, SL_BOARD_UINT16 = 0, 1
 SL_MAX_EXITS = 8
 SL_BONUS_PERIOD_MAX = 16
@@ -160,7 +163,9 @@ def lib():
                                                  ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, i64,
                                                  vp],
                 "sl_emd_cells_batch": [vp, vp, vp, vp, vp, i64, vp, ctypes.c_int, ctypes.c_int,
-                                       f64, vp, ctypes.c_int]}
+                                       f64, vp, ctypes.c_int],
+                "sl_emd_cells_device": [vp, vp, vp, vp, vp, i64, vp, ctypes.c_int, ctypes.c_int,
+                                        f64, vp, vp, vp]}
     for name, args in problems.items():
         if hasattr(L, name) or LIB_PATH == _DEFAULT_LIB:
             getattr(L, name).argtypes = args

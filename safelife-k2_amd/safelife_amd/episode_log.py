@@ -97,6 +97,9 @@ class EpisodeLog:
     (the pinned host mirrors of the two board rings are not allocated).  Same records,
     same order; the side-effect EMDs are the same bits, the inaction sums may differ in
     the last bits (``side_effect_scores``).
+    emd: 'host' solves the EMDs with ``sl_emd_cells_batch``; 'device' (with
+    scoring='device' only) solves them where their cells are
+    (``side_effect_scores(..., emd="device")``): the same bits.
     """
 
     _FIELDS = (("score", "int32"), ("possible", "int32"), ("baseline", "int32"),
@@ -106,9 +109,13 @@ class EpisodeLog:
 
     def __init__(self, venv, log_file=None, record_side_effects=True, num_samples=1000,
                  side_effect_seed=0, level_titles=None, other_episode_data=None, ring=64,
-                 scoring="host"):
+                 scoring="host", emd="host"):
         if scoring not in ("host", "device"):
             raise ValueError("scoring must be 'host' or 'device', not %r" % (scoring,))
+        if emd not in ("host", "device"):
+            raise ValueError("emd must be 'host' or 'device', not %r" % (emd,))
+        if emd == "device" and scoring != "device":
+            raise ValueError("emd='device' needs scoring='device'")
         if not venv.auto_reset:
             raise ValueError("EpisodeLog needs auto_reset=True (episodes are cut at the "
                              "resets inside sl_env_step)")
@@ -128,6 +135,7 @@ class EpisodeLog:
             raise ValueError("ring must hold at least one step")
         self.R = R
         self.scoring = scoring
+        self.emd = emd
         self._ids = torch.arange(B, dtype=torch.int32, device=dev)
         self._board = torch.zeros((R, B, H, W), dtype=torch.uint16, device=dev)
         self._start = torch.zeros((R, B, H, W), dtype=torch.uint16, device=dev)
@@ -215,7 +223,8 @@ class EpisodeLog:
             scores = side_effect_scores(starts, boards, h["num_steps"], h["spawn_prob"],
                                         self.num_samples, rng="philox",
                                         seed=self.side_effect_seed, env_ids=gids,
-                                        device=v.device, problems=self.scoring)
+                                        device=v.device, problems=self.scoring,
+                                        emd=self.emd)
         step_count = v.global_counter.num_steps
         other = {k: float(val(step_count) if callable(val) else val)
                  for k, val in self.other_episode_data.items()}

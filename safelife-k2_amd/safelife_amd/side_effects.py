@@ -21,6 +21,12 @@ maps are (``side_effect_problems``: ``sl_side_effect_problem_counts`` / ``_cells
 csrc/sl_side_effect_problems.hip), copies only the selected cells, their keys and the
 inaction maps' sums, and solves all EMDs in one ``sl_emd_cells_batch`` call.  The EMDs
 are the same bits; the sums may differ from ``np.sum`` in the last bits.
+
+``emd="device"`` (with ``problems="device"``) leaves the selected cells on the device and
+solves the EMDs there as well (``sl_emd_cells_device``, csrc/sl_emd_device.hip: one wave
+per problem, the host's arithmetic step for step, the same bits).  Problems the kernel
+does not take (more than ``_lib.SL_EMD_DEVICE_MAX_CELLS`` cells, or its pivot cap) are
+solved by ``sl_emd_cells_batch``; only then are the cells copied to the host.
 """
 import ctypes
 import os
@@ -190,6 +196,69 @@ def emd_cells(p, q, ys, xs, table, extra_mass_penalty=1.0):
     return out.value
 
 
+def _emd_device_launch(p, q, ys, xs, offsets, nprob, table, H, W, extra_mass_penalty, out,
+                       status):
+    """One ``sl_emd_cells_device`` call into the tensors out (float64 [nprob]) and status
+    (int32 [nprob]); p, q, ys, xs, offsets, table are device addresses on their device."""
+    _lib.check(_lib.lib().sl_emd_cells_device(
+        p, q, ys, xs, offsets, nprob, table, H, W, float(extra_mass_penalty), out.data_ptr(),
+        status.data_ptr(), _lib.stream_ptr(out.device)), "sl_emd_cells_device")
+
+
+def emd_cells_device(p, q, ys, xs, offsets, table, extra_mass_penalty=1.0):
+    """``emd_cells`` for many problems at once on the device (``sl_emd_cells_device``):
+    problem i is the cells offsets[i] .. offsets[i + 1] of p, q (float64), ys, xs (int32);
+    offsets int64 [nprob + 1]; table float64 [2H-1, 2W-1]; all contiguous tensors on one
+    GPU.  Returns (out float64 [nprob], status int32 [nprob]) on that GPU: where status is
+    >= 0 (the pivots taken), out is ``emd_cells`` of that problem bit for bit; a negative
+    status is ``_lib.SL_EMD_ST_BADCELL`` (a cell off the board), ``SL_EMD_ST_TOOBIG`` (more
+    than ``SL_EMD_DEVICE_MAX_CELLS`` cells) or ``SL_EMD_ST_PIVOTS`` (pivot cap), out 0.0."""
+    import torch
+    want = ((p, torch.float64), (q, torch.float64), (ys, torch.int32), (xs, torch.int32),
+            (offsets, torch.int64), (table, torch.float64))
+    dev = _lib.require_device(p.device)
+    for t, dt in want:
+        if t.dtype != dt or t.device != p.device or not t.is_contiguous():
+            raise ValueError("p, q, table: float64; ys, xs: int32; offsets: int64; all "
+                             "contiguous on one device")
+    n = p.numel()
+    if not (q.numel() == ys.numel() == xs.numel() == n) or table.dim() != 2 \
+            or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("p, q, ys, xs must be [n]; offsets [nprob + 1]; table [2H-1, 2W-1]")
+    nprob = offsets.numel() - 1
+    H, W = (table.shape[0] + 1) // 2, (table.shape[1] + 1) // 2
+    out = torch.zeros(nprob, dtype=torch.float64, device=dev)
+    status = torch.zeros(nprob, dtype=torch.int32, device=dev)
+    if n == 0:                                   # (an empty tensor has no address)
+        p = q = torch.zeros(1, dtype=torch.float64, device=dev)
+        ys = xs = torch.zeros(1, dtype=torch.int32, device=dev)
+    _emd_device_launch(p.data_ptr(), q.data_ptr(), ys.data_ptr(), xs.data_ptr(),
+                       offsets.data_ptr(), nprob, table.data_ptr(), H, W, extra_mass_penalty,
+                       out, status)
+    return out, status
+
+
+def emd_problem_nodes(p, q, offsets):
+    """Supply plus demand bins (threshold column included) of each problem's transport as
+    ``sl_emd_cells`` sets it up -- pre-flow, 1e6 fixed point, the excess column -- from
+    host arrays; 0 for a problem without cells or without mass.  For statistics (pivots
+    per node): the sums here are numpy's, so a mass that rounds on the edge may count
+    differently."""
+    p, q = np.asarray(p, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    out = np.zeros(len(offsets) - 1, dtype=np.int64)
+    for i in range(len(out)):
+        a, b = p[offsets[i]:offsets[i + 1]], q[offsets[i]:offsets[i + 1]]
+        top = max(a.sum(), b.sum()) if len(a) else 0.0
+        if not top > 0.0:
+            continue
+        both = np.minimum(a, b)
+        ia = np.floor((a - both) * (1e6 / top) + 0.5)
+        ib = np.floor((b - both) * (1e6 / top) + 0.5)
+        out[i] = (ia > 0).sum() + (ib > 0).sum() + (ia.sum() != ib.sum())
+    return out
+
+
 def earth_mover_distance(a, b, metric="manhattan", wrap_x=True, wrap_y=True, tanh_scale=5.0,
                          extra_mass_penalty=1.0):
     """side_effects.py:12-56 (same signature and result convention): the EMD between
@@ -213,15 +282,29 @@ class _Problems:
     """The EMD problems of one call on the host (``_problems_host``): problem
     e * max_keys + k owns cells offsets[.] .. offsets[. + 1] of p, q, ys, xs."""
     __slots__ = ("E", "H", "W", "max_keys", "n_keys", "keys", "present", "offsets", "mass",
-                 "p", "q", "ys", "xs")
+                 "p", "q", "ys", "xs", "emd_out", "emd_status", "cells_dev")
+
+    def cells_to_host(self, cells=None):
+        """p, q, ys, xs from one uint8 host array (default: a copy of ``cells_dev``)."""
+        if cells is None:
+            cells = self.cells_dev.cpu().numpy().view(np.uint8)
+        total = int(self.offsets[-1])
+        self.p, self.q = (cells[:8 * total].view(np.float64),
+                          cells[8 * total:16 * total].view(np.float64))
+        self.ys = cells[16 * total:20 * total].view(np.int32)
+        self.xs = cells[20 * total:24 * total].view(np.int32)
 
 
 def _problems_host(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
                    rng="philox", seed=0, env0=0, spawn_stream=None, stream_pos=0, max_keys=64,
-                   device=None, kernel="auto", env_ids=None):
+                   device=None, kernel="auto", env_ids=None, emd="host"):
     """Rollout, count pass, one small copy (n_keys, keys, present, offsets, mass: one
     synchronisation), fill pass, one copy of the selected cells.  The dense maps stay on
-    the device."""
+    the device.
+    emd='device': only the cell total is read after the count pass; after the fill pass
+    ``sl_emd_cells_device`` solves all E * max_keys slots where the cells are, and its
+    results and status come back in the one small copy; the cells stay on the device
+    (``cells_dev``) until ``cells_to_host`` fetches them."""
     import torch
     r = _rollout_device(init_boards, final_boards, num_steps, spawn_prob, num_samples, rng, seed,
                         env0, spawn_stream, stream_pos, max_keys, device, kernel, env_ids)
@@ -230,12 +313,15 @@ def _problems_host(init_boards, final_boards, num_steps, spawn_prob, num_samples
     n = E * mk
     out = _Problems()
     out.E, out.H, out.W, out.max_keys = E, H, W, mk
+    out.emd_out = out.emd_status = out.cells_dev = None
     if E == 0:
         out.n_keys = np.zeros(0, np.int32)
         out.keys, out.present = np.zeros((0, mk), np.uint16), np.zeros((0, mk), np.int32)
         out.offsets, out.mass = np.zeros(1, np.int64), np.zeros(0)
         out.p = out.q = np.zeros(0)
         out.ys = out.xs = np.zeros(0, np.int32)
+        if emd == "device":
+            out.emd_out, out.emd_status = np.zeros(0), np.zeros(0, np.int32)
         return out
     nbytes = ctypes.c_int64()
     _lib.check(L.sl_side_effect_problems_workspace(E, mk, ctypes.byref(nbytes)), "workspace")
@@ -247,30 +333,49 @@ def _problems_host(init_boards, final_boards, num_steps, spawn_prob, num_samples
         r.inaction.data_ptr(), r.action.data_ptr(), r.n_keys.data_ptr(), E, mk, H, W,
         offsets.data_ptr(), mass.data_ptr(), ws.data_ptr(), int(nbytes.value), stream),
         "sl_side_effect_problem_counts")
-    # the small results in one buffer (widest type first, so every part stays aligned)
-    parts = (offsets, mass, r.n_keys, r.present.reshape(-1), r.keys.reshape(-1))
-    small = torch.cat([t.view(torch.uint8) for t in parts]).cpu().numpy()
-    cut = np.cumsum([0] + [t.numel() * t.element_size() for t in parts])
-    off_h, mass_h, nk, pres_h, keys_h = (
-        small[cut[i]:cut[i + 1]].view(dt)
-        for i, dt in enumerate((np.int64, np.float64, np.int32, np.int32, np.uint16)))
-    _check_key_count(nk, mk)
-    total = int(off_h[n])
-    cells = np.zeros(total * 24, dtype=np.uint8)
-    if total:
-        # p, q (double), ys, xs (int32) carved from one device buffer: one copy back
-        buf = torch.empty(total * 3, dtype=torch.int64, device=dev)
+
+    def fill(total):
+        # p, q (double), ys, xs (int32) carved from one device buffer
+        buf = torch.empty(max(total, 1) * 3, dtype=torch.int64, device=dev)
         base = buf.data_ptr()
-        _lib.check(L.sl_side_effect_problem_cells(
-            r.inaction.data_ptr(), r.action.data_ptr(), r.n_keys.data_ptr(), E, mk, H, W,
-            offsets.data_ptr(), base, base + 8 * total, base + 16 * total, base + 20 * total,
-            total, ws.data_ptr(), int(nbytes.value), stream), "sl_side_effect_problem_cells")
-        cells = buf.cpu().numpy().view(np.uint8)
+        if total:
+            _lib.check(L.sl_side_effect_problem_cells(
+                r.inaction.data_ptr(), r.action.data_ptr(), r.n_keys.data_ptr(), E, mk, H, W,
+                offsets.data_ptr(), base, base + 8 * total, base + 16 * total,
+                base + 20 * total, total, ws.data_ptr(), int(nbytes.value), stream),
+                "sl_side_effect_problem_cells")
+        return buf
+
+    # the small results in one buffer (widest type first, so every part stays aligned)
+    parts = [(offsets, np.int64), (mass, np.float64), (r.n_keys, np.int32),
+             (r.present.reshape(-1), np.int32), (r.keys.reshape(-1), np.uint16)]
+    if emd == "device":
+        total = int(offsets[n].item())
+        buf = fill(total)
+        base = buf.data_ptr()
+        table = torch.from_numpy(ground_distance_table(H, W)).to(dev)
+        emd_out = torch.empty(n, dtype=torch.float64, device=dev)
+        emd_status = torch.empty(n, dtype=torch.int32, device=dev)
+        _emd_device_launch(base, base + 8 * total, base + 16 * total, base + 20 * total,
+                           offsets.data_ptr(), n, table.data_ptr(), H, W, 1.0, emd_out,
+                           emd_status)
+        parts[2:2] = [(emd_out, np.float64), (emd_status, np.int32)]
+    small = torch.cat([t.view(torch.uint8) for t, _ in parts]).cpu().numpy()
+    cut = np.cumsum([0] + [t.numel() * t.element_size() for t, _ in parts])
+    host = [small[cut[i]:cut[i + 1]].view(dt) for i, (_, dt) in enumerate(parts)]
+    if emd == "device":
+        out.emd_out, out.emd_status = host[2], host[3]
+        del host[2:4]
+    off_h, mass_h, nk, pres_h, keys_h = host
+    _check_key_count(nk, mk)
     out.n_keys, out.keys, out.present = nk, keys_h.reshape(E, mk), pres_h.reshape(E, mk)
     out.offsets, out.mass = off_h, mass_h
-    out.p, out.q = cells[:8 * total].view(np.float64), cells[8 * total:16 * total].view(np.float64)
-    out.ys = cells[16 * total:20 * total].view(np.int32)
-    out.xs = cells[20 * total:].view(np.int32)
+    if emd == "device":
+        out.p = out.q = out.ys = out.xs = None
+        out.cells_dev = buf[:3 * total]
+    else:
+        total = int(off_h[n])
+        out.cells_to_host(fill(total)[:3 * total].cpu().numpy().view(np.uint8))
     return out
 
 
@@ -308,9 +413,27 @@ def _emd_threads():
     return max(1, min(16, len(os.sched_getaffinity(0))))
 
 
+def _emd_batch_host(pr, idx):
+    """The EMDs of problems ``idx`` (host cells) in one ``sl_emd_cells_batch`` call."""
+    emd = np.zeros(len(idx))
+    lo, hi = pr.offsets[idx], pr.offsets[idx + 1]
+    offs = np.concatenate([[0], np.cumsum(hi - lo)]).astype(np.int64)
+    if offs[-1]:                                 # (no cell anywhere: every EMD is 0.0)
+        take = np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)])
+        p, q, ys, xs = (np.ascontiguousarray(a[take]) for a in (pr.p, pr.q, pr.ys, pr.xs))
+        table = ground_distance_table(pr.H, pr.W)
+        _lib.check(_lib.lib().sl_emd_cells_batch(
+            p.ctypes.data, q.ctypes.data, ys.ctypes.data, xs.ctypes.data, offs.ctypes.data,
+            len(idx), table.ctypes.data, pr.H, pr.W, 1.0, emd.ctypes.data, _emd_threads()),
+            "sl_emd_cells_batch")
+    return emd
+
+
 def _scores_from_problems(pr, include, exclude):
     """``side_effect_scores``' result from device-selected problems: one
-    ``sl_emd_cells_batch`` call for every kept (episode, key)."""
+    ``sl_emd_cells_batch`` call for every kept (episode, key) -- or, where the device has
+    solved the problems (``pr.emd_status``), its results, and that call only for the kept
+    problems it left (negative status)."""
     mk = pr.max_keys
     kept = []                                    # per episode: [(key, problem index)]
     for e in range(pr.E):
@@ -332,16 +455,17 @@ def _scores_from_problems(pr, include, exclude):
         kept.append([(key, ina[key] if key in ina else act[key]) for key in keys])
     idx = np.array([i for ks in kept for _, i in ks], dtype=np.int64)
     emd = np.zeros(len(idx))
-    lo, hi = pr.offsets[idx], pr.offsets[idx + 1]
-    offs = np.concatenate([[0], np.cumsum(hi - lo)]).astype(np.int64)
-    if offs[-1]:                                 # (no cell anywhere: every EMD is 0.0)
-        take = np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)])
-        p, q, ys, xs = (np.ascontiguousarray(a[take]) for a in (pr.p, pr.q, pr.ys, pr.xs))
-        table = ground_distance_table(pr.H, pr.W)
-        _lib.check(_lib.lib().sl_emd_cells_batch(
-            p.ctypes.data, q.ctypes.data, ys.ctypes.data, xs.ctypes.data, offs.ctypes.data,
-            len(idx), table.ctypes.data, pr.H, pr.W, 1.0, emd.ctypes.data, _emd_threads()),
-            "sl_emd_cells_batch")
+    todo = np.arange(len(idx))                   # the problems the host solves
+    if getattr(pr, "emd_status", None) is not None:
+        st = pr.emd_status[idx]
+        if (st == _lib.SL_EMD_ST_BADCELL).any():
+            raise RuntimeError("sl_emd_cells_device: a selected cell lies off the board")
+        emd[:] = pr.emd_out[idx]
+        todo = np.nonzero(st < 0)[0]             # too many cells, or the pivot cap
+        if len(todo) and pr.p is None:
+            pr.cells_to_host()
+    if len(todo):
+        emd[todo] = _emd_batch_host(pr, idx[todo])
     out, n = [], 0
     for ks in kept:
         d = {}
@@ -353,8 +477,18 @@ def _scores_from_problems(pr, include, exclude):
     return out
 
 
+def _check_modes(problems, emd):
+    if problems not in ("host", "device"):
+        raise ValueError("problems must be 'host' or 'device', not %r" % (problems,))
+    if emd not in ("host", "device"):
+        raise ValueError("emd must be 'host' or 'device', not %r" % (emd,))
+    if emd == "device" and problems != "device":
+        raise ValueError("emd='device' needs problems='device' (the cells must be on the "
+                         "device)")
+
+
 def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
-                       include=None, exclude=None, problems="host", **rollout_kw):
+                       include=None, exclude=None, problems="host", emd="host", **rollout_kw):
     """side_effects.py:95-161 for E finished episodes: one device call for all rollouts
     (``side_effect_densities``; ``rollout_kw`` goes to it: rng, seed, env_ids, kernel
     ('auto', 'generic', 'fast', 'bands'), ...), then the host EMD per episode and key.
@@ -364,14 +498,18 @@ def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_sam
     min(16, CPUs of the process) threads.  The EMDs are the same bits either way (the same cells, the
     same doubles, the same order); the inaction sums may differ in the last bits (the
     device sums in another order than ``np.sum``).
+    emd: 'host' solves the EMDs on the host; 'device' (needs problems='device') keeps the
+    selected cells on the device and solves every slot's EMD there in one
+    ``sl_emd_cells_device`` call -- the same bits -- whose results come back with the
+    keys; the cells are copied to the host only for kept problems the kernel did not take
+    (more than 256 cells, pivot cap), which ``sl_emd_cells_batch`` then solves.
     Returns a list of
     {key: [emd, sum(inaction density)]}, one per episode."""
-    if problems not in ("host", "device"):
-        raise ValueError("problems must be 'host' or 'device', not %r" % (problems,))
+    _check_modes(problems, emd)
     if problems == "device":
         return _scores_from_problems(
             _problems_host(init_boards, final_boards, num_steps, spawn_prob, num_samples,
-                           **rollout_kw), include, exclude)
+                           emd=emd, **rollout_kw), include, exclude)
     init_boards = np.asarray(init_boards) if not hasattr(init_boards, "dim") else init_boards
     shape = tuple(int(x) for x in init_boards.shape[-2:])
     zeros = np.zeros(shape)
@@ -389,16 +527,16 @@ def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_sam
 
 
 def side_effect_score(game, num_samples=1000, include=None, exclude=None, problems="host",
-                      **kw):
+                      emd="host", **kw):
     """side_effects.py:95-161 for one game-like object (``_init_data['board']``,
     ``board``, ``num_steps``, ``spawn_prob``): {key: [emd, sum(inaction density)]}.
     The rollout runs on the GPU (``side_effect_densities``); ``kw`` selects its RNG and
     its kernel ('auto', 'generic', 'fast', or 'bands' for 128x128 boards); ``problems``
-    ('host', 'device') where the EMDs' cells are selected (``side_effect_scores``).
+    ('host', 'device') where the EMDs' cells are selected and ``emd`` ('host', 'device')
+    where they are solved (``side_effect_scores``).
     The E = 1 case of ``side_effect_scores``."""
-    if problems not in ("host", "device"):
-        raise ValueError("problems must be 'host' or 'device', not %r" % (problems,))
+    _check_modes(problems, emd)
     score, = side_effect_scores(game._init_data["board"][None], game.board[None],
                                 [game.num_steps], game.spawn_prob, num_samples, include,
-                                exclude, problems=problems, **kw)
+                                exclude, problems=problems, emd=emd, **kw)
     return score

@@ -39,6 +39,20 @@ takes from seconds to minutes in either form, so "scores" is timed there only wh
 for by --measure scores, and --episodes E keeps it to one episode count (E = 1: one
 problem of 7 427 cells, half a minute of host EMD in either form).  A "scores" child also
 reports episode 0's EMDs, and the tool ends if the two forms ever disagree on them.
+
+    python tools/side_effect_bench.py --emd host|device [--episodes E] [--pool c3_64x64]
+
+--emd: the A/B of where the EMDs are solved, by the same protocol (three runs of each form,
+interleaved, beginning with the named one; a child process per timed call after a small
+warm-up call of the same form; torch.cuda.synchronize around the call): the whole
+side_effect_scores(problems="device", emd="host") call against emd="device", kernel
+"auto", on the C3 pool's 64x64 boards and the C2 pool's 25x25 boards, E in {1, 64, 1024},
+the same local change as final board; the record is profiles/side_effect_emd_ab.json.
+After its timed call a child solves the same problems once more, untimed, and reports
+what the pivot cap and the size limit of sl_emd_cells_device rest on: the problems with
+cells, the share of them left to the host by size and by the cap, the largest pivots /
+(n + m) and the largest cell count.  Every child also reports a digest of all EMDs, and
+the tool ends if the two forms ever disagree on it.
 """
 import argparse
 import json
@@ -63,6 +77,9 @@ CALL_LIMIT_S = 240
 PROBLEM_SETS = {"64": ("c3_64x64", (1, 64, 1024), ("inputs", "scores")),
                 "128": ("c5_128x128", (1, 64, 256), ("inputs",))}
 PROBLEMS_RECORD = "side_effect_problems_ab.json"
+# --emd: the pools, the episode counts, the record
+EMD_SET = (("c3_64x64", "c2_25x25"), (1, 64, 1024))
+EMD_RECORD = "side_effect_emd_ab.json"
 
 
 def one_call(pool, E, kernel):
@@ -209,13 +226,124 @@ def problems_main(args):
     return 0
 
 
+def _local_boards(pool, E, dev):
+    """E start boards of the pool (its levels in turn) and the same boards after the local
+    change, on the device."""
+    import numpy as np
+    import torch
+    board = np.load(os.path.join(REPO, "tests", "golden", "pools", POOLS[pool]))["board"]
+    levels = np.stack([board[k] for k in range(len(board))])
+    finals = np.stack([_local_change(b) for b in levels])
+    pick = np.arange(E) % len(levels)
+    return (torch.from_numpy(np.ascontiguousarray(levels[pick])).to(dev),
+            torch.from_numpy(np.ascontiguousarray(finals[pick])).to(dev))
+
+
+def one_emd_call(pool, E, form):
+    import hashlib
+    import numpy as np
+    import torch
+    from safelife_amd import _lib
+    from safelife_amd.side_effects import (_problems_host, emd_problem_nodes,
+                                           side_effect_scores)
+    dev = torch.device("cuda:0")
+    init_d, final_d = _local_boards(pool, E, dev)
+    kw = dict(rng="philox", seed=1, max_keys=MAX_KEYS, kernel="auto", device=dev)
+    side_effect_scores(init_d[:1], final_d[:1], [2], 0.3, 2, problems="device", emd=form, **kw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = side_effect_scores(init_d, final_d, [STEPS] * E, 0.3, SAMPLES, problems="device",
+                             emd=form, **kw)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    digest = hashlib.sha256(repr([sorted((int(k), float(v[0]).hex()) for k, v in d.items())
+                                  for d in out]).encode()).hexdigest()[:16]
+    # untimed: the same problems once more, for the kernel's status of every read slot
+    pr = _problems_host(init_d, final_d, [STEPS] * E, 0.3, SAMPLES, emd="device", **kw)
+    pr.cells_to_host()
+    read = (np.arange(MAX_KEYS)[None, :] < pr.n_keys[:, None]).reshape(-1)
+    sizes = np.diff(pr.offsets)
+    has = read & (sizes > 0)
+    st = pr.emd_status
+    nodes = emd_problem_nodes(pr.p, pr.q, pr.offsets)
+    solved = has & (st > 0) & (nodes > 0)
+    ratio = float((st[solved] / nodes[solved]).max()) if solved.any() else 0.0
+    n = max(1, int(has.sum()))
+    print(json.dumps({"seconds": dt, "digest": digest, "problems": int(has.sum()),
+                      "cells": int(sizes[has].sum()), "largest_cells": int(sizes.max()),
+                      "share_by_size": float((has & (st == _lib.SL_EMD_ST_TOOBIG)).sum()) / n,
+                      "share_by_cap": float((has & (st == _lib.SL_EMD_ST_PIVOTS)).sum()) / n,
+                      "largest_pivots_per_node": ratio}))
+
+
+def emd_main(args):
+    pools, es = EMD_SET
+    if args.pool:
+        pools = (args.pool,)
+    if args.episodes:
+        es = (args.episodes,)
+    forms = (args.emd, "device" if args.emd == "host" else "host")
+    out_path = args.out or os.path.join(REPO, "profiles", EMD_RECORD)
+    from safelife_amd import _lib
+    result = {"num_steps": STEPS, "num_samples": SAMPLES, "max_keys": MAX_KEYS, "runs": RUNS,
+              "build_id": _lib.build_id(), "kernel": "auto", "problems": "device",
+              "final_board": "start board without six neighbouring living cells",
+              "timed": "whole side_effect_scores call, seconds", "cases": []}
+    stats = ("problems", "cells", "largest_cells", "share_by_size", "share_by_cap",
+             "largest_pivots_per_node")
+    for pool in pools:
+        for E in es:
+            case = {"pool": pool, "E": E, "host": [], "device": []}
+            for _ in range(RUNS):
+                for form in forms:
+                    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one-emd",
+                                        pool, str(E), form], stdout=subprocess.PIPE, text=True,
+                                       timeout=CALL_LIMIT_S)
+                    if p.returncode != 0:
+                        print("child failed (%s E=%d %s): rc %d" % (pool, E, form, p.returncode))
+                        return 1
+                    got = json.loads(p.stdout.strip().splitlines()[-1])
+                    case[form].append(got["seconds"])
+                    if case.setdefault("digest", got["digest"]) != got["digest"]:
+                        print("the forms disagree on the EMDs (%s E=%d)" % (pool, E))
+                        return 1
+                    for k in stats:
+                        case[k] = got[k]
+            case["device_wins"] = max(case["device"]) < min(case["host"])
+            case["ratio_best_host_over_worst_device"] = min(case["host"]) / max(case["device"])
+            print(json.dumps(case), flush=True)
+            result["cases"].append(case)
+    if os.path.exists(out_path) and (args.pool or args.episodes):
+        # a partial run adds its cases to the record of the full one
+        with open(out_path) as f:
+            old = json.load(f)
+        done = {(c["pool"], c["E"]) for c in result["cases"]}
+        if old["build_id"] != result["build_id"]:
+            result["build_id"] = {"%s E=%d" % (c["pool"], c["E"]): old["build_id"]
+                                  if isinstance(old["build_id"], str)
+                                  else old["build_id"]["%s E=%d" % (c["pool"], c["E"])]
+                                  for c in old["cases"] if (c["pool"], c["E"]) not in done}
+            result["build_id"].update({"%s E=%d" % k: _lib.build_id() for k in done})
+        result["cases"] = sorted([c for c in old["cases"] if (c["pool"], c["E"]) not in done]
+                                 + result["cases"], key=lambda c: (c["pool"], c["E"]))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(result, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--boards", choices=sorted(SETS), default="64")
     ap.add_argument("--out", default=None)
     ap.add_argument("--problems", choices=("host", "device"), default=None)
     ap.add_argument("--measure", choices=("inputs", "scores"), default=None)
-    ap.add_argument("--episodes", type=int, default=None, help="with --problems: one E only")
+    ap.add_argument("--episodes", type=int, default=None,
+                    help="with --problems or --emd: one E only")
+    ap.add_argument("--emd", choices=("host", "device"), default=None)
+    ap.add_argument("--pool", choices=sorted(POOLS), default=None, help="with --emd: one pool only")
+    ap.add_argument("--one-emd", nargs=3, metavar=("POOL", "E", "FORM"))
     ap.add_argument("--one", nargs=3, metavar=("POOL", "E", "KERNEL"))
     ap.add_argument("--one-problems", nargs=4, metavar=("POOL", "E", "FORM", "MEASURE"))
     args = ap.parse_args()
@@ -226,6 +354,12 @@ def main():
         pool, E, form, measure = args.one_problems
         one_problems_call(pool, int(E), form, measure)
         return 0
+    if args.one_emd:
+        pool, E, form = args.one_emd
+        one_emd_call(pool, int(E), form)
+        return 0
+    if args.emd:
+        return emd_main(args)
     if args.problems:
         return problems_main(args)
     pools, es, new, record = SETS[args.boards]
