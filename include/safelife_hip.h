@@ -86,6 +86,10 @@ extern "C" {
 #define SL_BOARD_AUTO 0
 #define SL_BOARD_UINT16 1
 
+/* sl_env_cfg.planes64_waves, beside 0, 5 and 6: the six-wave 64x64 plane kernel with its
+ * epilogue in the wave and the reset list, where the default splits them off */
+#define SL_PLANES64_W6_UNSPLIT (-6)
+
 #define SL_MAX_EXITS 8      /* exits tracked per env (benchmark levels have 1) */
 #define SL_BONUS_PERIOD_MAX 16
 
@@ -752,7 +756,16 @@ typedef struct sl_env_cfg {
     int32_t planes64_waves;         /* 64x64 plane mode, C3 / C4 planes, gray goals,
                                        no views: 0 or 6, the kernel sized for six
                                        waves per SIMD; 5, its five-wave twin (same
-                                       results; kept for comparison)           */
+                                       results; kept for comparison).  With
+                                       auto_reset from a pool (and no capture) the
+                                       six-wave kernel ends each wave after its plane
+                                       stores and a second kernel runs the epilogue
+                                       one lane per env and resets the finished envs
+                                       (the 32 B per env handed over lie in scratch
+                                       words [4B, 8B), which must be 16-byte aligned);
+                                       SL_PLANES64_W6_UNSPLIT keeps the six-wave
+                                       kernel with the epilogue in the wave and the
+                                       reset list (same results; for comparison) */
 } sl_env_cfg;
 
 /*

@@ -786,5 +786,36 @@ __device__ __forceinline__ void queue_reset(int64_t *scratch, int64_t B, uint32_
     reset_list(scratch)[i] = (int32_t)b;
 }
 
+// The hand-over record of env b, from a step kernel that ends after its stores to the
+// kernel that runs the epilogue one lane per env (k_env_epilogue_reset64, sl_bits.hip):
+// what epilogue_core takes from the step's wave and cannot re-read from the state arrays.
+// 32 B per env in the scratch words [4B, 8B) (Scratch.act: unused by a Philox plane step),
+// written and read as two 16-byte words.
+struct Handover {
+    int act_reward, points, score, possible, side;   // the action's reward, the new totals
+    int go, ax, ay;                                  // game_over and the agent after the action
+};
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ i32x4 *handover_of(int64_t *scratch, int64_t B) {
+    return reinterpret_cast<i32x4 *>(scratch + 4 * B);
+}
+__device__ __forceinline__ void put_handover(i32x4 *hv, int64_t b, const Handover &h) {
+    hv[2 * b] = i32x4{h.act_reward, h.points, h.score, h.possible};
+    hv[2 * b + 1] = i32x4{h.side, h.go, h.ax, h.ay};
+}
+__device__ __forceinline__ Handover get_handover(const i32x4 *hv, int64_t b) {
+    const i32x4 u = hv[2 * b], v = hv[2 * b + 1];
+    return Handover{u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+}
+
+// the epilogue's view in that kernel: the env's fields from the state arrays (one lane per
+// env: the reads coalesce), game_over and the agent from the hand-over record
+struct HandFields : GlobalFields {
+    int go, ax, ay;
+    __device__ int game_over() const { return go; }
+    __device__ int agent_x() const { return ax; }
+    __device__ int agent_y() const { return ay; }
+};
+
 }  // namespace bits
 }  // namespace sl

@@ -987,7 +987,7 @@ __global__ void __launch_bounds__(64, planes_min_waves(K16, OBS))
 k_env_step_bits64_planes(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     uint16_t *const vm = nullptr;
-    constexpr bool GRAY = false, W6 = false;
+    constexpr bool GRAY = false, W6 = false, SPLIT_EPI = false;
 #include "sl_planes64_step.inc"
 }
 
@@ -1003,7 +1003,7 @@ k_env_planes64_gray(StepKArgs ka) {
     static_assert(OBS <= 1, "channel views load the three colour planes");
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     uint16_t *const vm = nullptr;
-    constexpr bool GRAY = true, W6 = false;
+    constexpr bool GRAY = true, W6 = false, SPLIT_EPI = false;
 #include "sl_planes64_step.inc"
 }
 
@@ -1023,8 +1023,73 @@ k_env_planes64_w6(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) u32 stage[kStageDwW6];
     uint16_t *const vm = nullptr;
     constexpr int OBS = 0;
-    constexpr bool GRAY = true, W6 = true;
+    constexpr bool GRAY = true, W6 = true, SPLIT_EPI = false;
 #include "sl_planes64_step.inc"
+}
+
+// k_env_planes64_w6 without its one-lane tail: after the plane stores lane 0 writes the
+// env's hand-over record (Handover, sl_bits.h) and the wave ends; the epilogue and the
+// resets run in k_env_epilogue_reset64 below, launched right after.  Same registers and
+// buffer; launched only with auto-reset from a pool (launch_step_bits).  (Named apart from
+// k_env_planes64_w6, whose resource test counts by name;
+// tests/test_kernel_resources_split.py.)
+template <u32 K16>
+__global__ void __launch_bounds__(64, kMinWavesW6)
+k_env_planes64_s6(StepKArgs ka) {
+    __shared__ __attribute__((aligned(16))) u32 stage[kStageDwW6];
+    uint16_t *const vm = nullptr;
+    constexpr int OBS = 0;
+    constexpr bool GRAY = true, W6 = true, SPLIT_EPI = true;
+#include "sl_planes64_step.inc"
+}
+
+// The epilogue of every env k_env_planes64_s6 stepped, one lane per env (in the step's
+// wave it ran on lane 0 while 63 lanes idled and the wave held its registers and LDS), then
+// the resets of the envs that finished: each wave ballots the lanes whose env finished,
+// and the block's four waves take its finished envs in turn, all 64 lanes resetting one
+// env (wave_reset, as k_env_reset_list runs it).  No list in memory and no shared counter;
+// the reset-list lengths stay zero, and the other step parity's is zeroed as
+// k_env_reset_list does.
+constexpr int kTailThreads = 256;
+__global__ void __launch_bounds__(kTailThreads)
+k_env_epilogue_reset64(sl_env_state st, StepArgs a, sl_level_pool pool, ResetArgs ra,
+                       int64_t *scratch, double *reward_out, uint8_t *done_out,
+                       uint8_t *flags_out, int32_t *ep_len_out, int32_t *ep_rew_out) {
+    const int64_t b = (int64_t)blockIdx.x * kTailThreads + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    if (b == 0) scratch[8 * st.B + 2 + ((a.step + 1) & 1)] = 0;
+    bool reset = false;
+    if (b < st.B) {
+        const Handover h = get_handover(handover_of(scratch, st.B), b);
+        const HandFields f{{st, b, a.bonus_table}, h.go, h.ax, h.ay};
+        reset = epilogue_core(st, a, b, f, h.act_reward, h.points, h.score, h.possible, h.side,
+                              reward_out, done_out, flags_out, ep_len_out, ep_rew_out);
+    }
+    // the block's finished envs, dealt round its four waves in env order: two in one
+    // wave's 64 (a few waves every step at 65 536 envs) do not wait for each other
+    __shared__ uint64_t finished[kTailThreads / 64];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t mine = __ballot(reset);
+    if (lane == 0) finished[wave] = mine;
+    // the epilogue's stores before the resets' to the same words (the env's scalars, its
+    // exit cells), which other lanes -- of any wave of the block -- issue: retired at
+    // workgroup scope (the block's waves store through one CU to one L2; a device-scope
+    // fence in every wave, with its L2 write-back, cost more than the step kernel gained)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    const int64_t b0 = (int64_t)blockIdx.x * kTailThreads;
+    int i = 0;
+#pragma unroll 1
+    for (int q = 0; q < kTailThreads / 64; q++) {
+        const uint64_t f = finished[q];
+        uint64_t todo = ((uint64_t)(u32)__builtin_amdgcn_readfirstlane((int)(f >> 32)) << 32) |
+                        (u32)__builtin_amdgcn_readfirstlane((int)f);
+        while (todo) {
+            const int k = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            if ((i++ & (kTailThreads / 64 - 1)) == wave) wave_reset(st, pool, ra, b0 + 64 * q + k, lane);
+        }
+    }
 }
 
 // Plane mode with channel views of ESZ-byte elements (1: u8, 2: u16 / bf16, 4: f32): the
@@ -1039,7 +1104,7 @@ k_env_planes64_chan(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     __shared__ __attribute__((aligned(16))) uint16_t vmask[sl::obs::kFusedChanCells];
     uint16_t *const vm = vmask;
-    constexpr bool GRAY = false, W6 = false;
+    constexpr bool GRAY = false, W6 = false, SPLIT_EPI = false;
 #include "sl_planes64_step.inc"
 }
 
@@ -1221,6 +1286,7 @@ int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra 
     if (st.H != N || st.W != N) return SL_ETOOBIG;
     const unsigned grid = (unsigned)st.B;
     const StepKArgs ka{st, a, fx, actions, ctp, ctc, reward, done, flags, ep_len, ep_rew};
+    bool split = false;      // the step kernel left the epilogue and the resets to a tail kernel
     if (fx.obs_out && (fx.obs_vh < 1 || fx.obs_vw < 1 || fx.obs_vh * fx.obs_vw > 4096))
         return SL_EINVAL;
     if (fx.stream) {
@@ -1242,6 +1308,12 @@ int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra 
             u32 keep = ~st.board_zero & 0xFFFFu;
             if (keep == kKeepC3) keep = st.agent_planes == kAgentC3 ? kKeepC3Fixed : 0u;
             const int kind = obs_kind(fx);
+            // the six-wave kernel's split pair (k_env_planes64_s6 + k_env_epilogue_reset64):
+            // auto-reset from a pool, no views, no capture (its launch must see the flags
+            // before the resets); planes64_waves -6 keeps the epilogue in the wave
+            split = keep == kKeepC3Fixed && st.goals_gray && kind == 0 && planes64_waves != 5 &&
+                    planes64_waves != SL_PLANES64_W6_UNSPLIT && fx.fuse_reset && fx.pool.K > 0 &&
+                    !fx.capture && fx.scratch && (reinterpret_cast<uintptr_t>(fx.scratch) & 15) == 0;
             if (kind >= 2) {
                 launch_planes64_chan(keep, obs_esz(kind), grid, ka, s);
             } else if (keep == kKeepC3Fixed && st.goals_gray) {
@@ -1250,6 +1322,8 @@ int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra 
                     hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 1>), dim3(grid), dim3(64), 0, s, ka);
                 else if (planes64_waves == 5)  // (sl_env_cfg.planes64_waves: the five-wave twin)
                     hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 0>), dim3(grid), dim3(64), 0, s, ka);
+                else if (split)
+                    hipLaunchKernelGGL((k_env_planes64_s6<kKeepC3>), dim3(grid), dim3(64), 0, s, ka);
                 else
                     hipLaunchKernelGGL((k_env_planes64_w6<kKeepC3>), dim3(grid), dim3(64), 0, s, ka);
             } else if (fx.obs_out) {
@@ -1276,7 +1350,11 @@ int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra 
         const int rc = launch_capture(st, *fx.capture, flags, 0, s);
         if (rc) return rc;
     }
-    if (fx.fuse_reset && fx.pool.K > 0) {
+    if (split) {
+        const unsigned tgrid = (unsigned)((st.B + kTailThreads - 1) / kTailThreads);
+        hipLaunchKernelGGL(k_env_epilogue_reset64, dim3(tgrid), dim3(kTailThreads), 0, s, st, a,
+                           fx.pool, fx.ra, fx.scratch, reward, done, flags, ep_len, ep_rew);
+    } else if (fx.fuse_reset && fx.pool.K > 0) {
         const unsigned grid = (unsigned)(st.B < 512 ? st.B : 512);
         sl::obs::ObsArgs oa{};
         oa.vh = fx.obs_vh;

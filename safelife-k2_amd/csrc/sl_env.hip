@@ -1057,7 +1057,8 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
     // completes (and demotes) it.  (Replay: with draw planes, the decided form.)
     const bool planes128 = st->board_planes && st->planes_ok && st->H == 128 && st->W == 128;
     if (cfg->board_mode != SL_BOARD_AUTO && cfg->board_mode != SL_BOARD_UINT16) return SL_EINVAL;
-    if (cfg->planes64_waves != 0 && cfg->planes64_waves != 5 && cfg->planes64_waves != 6)
+    if (cfg->planes64_waves != 0 && cfg->planes64_waves != 5 && cfg->planes64_waves != 6 &&
+        cfg->planes64_waves != SL_PLANES64_W6_UNSPLIT)
         return SL_EINVAL;
     const bool fuse_obs128 = fast128 && planes128 && cfg->obs_out && !cap &&
                              cfg->board_mode != SL_BOARD_UINT16 &&

@@ -14,7 +14,8 @@ namespace sl {
 //             cell edits (the generic path; the bit-sliced replay prologues write
 //             the reward only; 128x128 replay with elig_planes: [B, 2B) holds the
 //             rows the action edited, then the tensors that draw, bit0 board, bit1 goals;
-//             [2B, 3B) the count of the board eligibility the step left)
+//             [2B, 3B) the count of the board eligibility the step left; the split
+//             six-wave 64x64 plane step: the env's hand-over record, sl_bits.h Handover)
 //   [8B]      error flags (bit0: draw stream exhausted)
 //   [8B+2], [8B+3]  reset-list lengths for even / odd steps (each step's reset
 //             kernel zeroes the other one)

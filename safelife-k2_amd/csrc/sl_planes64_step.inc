@@ -13,7 +13,9 @@
 // view's channel masks in LDS (uint16_t[kFusedChanCells]; unused when OBS < 2), and the
 // constant W6 (k_env_planes64_w6's: `stage` is 6 KiB, not 8 -- the pool's start-plane rows
 // are packed, a uint16 board is staged in two passes of 32 rows, and the scores read the
-// start planes one column word at a time; OBS == 0).
+// start planes one column word at a time; OBS == 0), and the constant SPLIT_EPI
+// (k_env_planes64_s6's: the wave ends after its stores with the env's hand-over record, and
+// k_env_epilogue_reset64 runs the epilogue and the resets, one lane per env).
 // With views, the goal colours are added into planes 12-14 (a bit-sliced adder, exact
 // whatever the board's bits), ONE transpose puts the view-form rows into the buffer.
     const sl_env_state &st = ka.st;
@@ -268,6 +270,14 @@
         else write_obs(buf, fx, fl, b, lane);
         __builtin_amdgcn_sched_barrier(0);
     }
+    if (SPLIT_EPI) {
+        // the epilogue runs in k_env_epilogue_reset64, one lane per env: what it cannot
+        // re-read from the state arrays goes out in the env's hand-over record
+        if (lane == 0)
+            put_handover(handover_of(fx.scratch, st.B), b,
+                         Handover{act_reward, tot.points, tot.score, tot.possible, tot.side,
+                                  fl.go, fl.ax, fl.ay});
+    } else {
     int reset = 0;
     if (lane == 0)
         reset = epilogue_core(st, a, b, fl, act_reward, tot.points, tot.score, tot.possible,
@@ -275,3 +285,4 @@
                               ka.ep_rew_out);
     reset = __builtin_amdgcn_readfirstlane(reset);
     if (fx.fuse_reset && reset && lane == 0) queue_reset(fx.scratch, st.B, a.step, b);
+    }

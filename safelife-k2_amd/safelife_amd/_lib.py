@@ -21,6 +21,7 @@ SL_STREAM_ERR_RANGE, SL_STREAM_ERR_THRESHOLD = 1, 2
 SL_EMD_DEVICE_MAX_CELLS = 256
 SL_EMD_ST_BADCELL, SL_EMD_ST_TOOBIG, SL_EMD_ST_PIVOTS = -1, -2, -3
 SL_BOARD_AUTO, SL_BOARD_UINT16 = 0, 1
+SL_PLANES64_W6_UNSPLIT = -6
 SL_MAX_EXITS = 8
 SL_BONUS_PERIOD_MAX = 16
 SL_OBS_NONE, SL_OBS_PACKED, SL_OBS_CHANNELS, SL_OBS_CHANNELS_U8 = 0, 1, 2, 3

@@ -180,9 +180,12 @@ class SafeLifeVecEnv:
         self.board_mode = board_mode
         # the 64x64 plane kernel of a C3 / C4 batch with gray goals and no views
         # (sl_env_cfg.planes64_waves): 6, the kernel sized for six waves per SIMD, or 5,
-        # its five-wave twin -- same results, kept for comparison
-        if planes64_waves not in (5, 6):
-            raise ValueError("planes64_waves must be 5 or 6")
+        # its five-wave twin -- same results, kept for comparison.  With auto_reset the
+        # six-wave kernel hands each env's epilogue and the resets to a second kernel (one
+        # lane per env; the hand-over records lie in `scratch`); -6
+        # (SL_PLANES64_W6_UNSPLIT) keeps them in the step's wave and the reset list
+        if planes64_waves not in (5, 6, _lib.SL_PLANES64_W6_UNSPLIT):
+            raise ValueError("planes64_waves must be 5, 6 or -6")
         self.planes64_waves = planes64_waves
         self._board_read_at = None   # step index of the last `board` read
         self._step_index = 0
