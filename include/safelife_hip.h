@@ -58,8 +58,8 @@ extern "C" {
                                cells of a 2x2 block share one evaluation,
                                counter (block, env, step, tensor), 32-bit words */
 
-#define SL_KERNEL_AUTO 0     /* bit-sliced kernels for 64x64, 128x128 and boards
-                                up to 32x64 (both RNG modes; replay adds an
+#define SL_KERNEL_AUTO 0     /* bit-sliced kernels for 128x128 and for boards of
+                                up to 64 rows x 64 columns (both RNG modes; replay adds an
                                 action kernel, a count kernel and a scan per
                                 step), the generic
                                 kernel for other shapes                      */
@@ -70,6 +70,14 @@ extern "C" {
                                 SL_ETOOBIG elsewhere.  Accepted by
                                 sl_side_effect_densities_k only
                                 (sl_env_cfg.kernel: SL_EINVAL)                */
+
+/* the step kernel families of sl_env_step (sl_env_step_family) */
+#define SL_FAMILY_GENERIC 0     /* k_env_action + the per-cell kernel, any shape      */
+#define SL_FAMILY_SMALL_SEG4 1  /* bit-sliced, H <= 32, W <= 32: four envs per wave   */
+#define SL_FAMILY_SMALL 2       /* bit-sliced, H <= 32, 32 < W <= 64                  */
+#define SL_FAMILY_MID 3         /* bit-sliced, 33 <= H <= 64, W <= 64, 64x64 aside    */
+#define SL_FAMILY_BITS64 4      /* bit-sliced 64x64 kernels                           */
+#define SL_FAMILY_BITS128 5     /* bit-sliced 128x128 kernels                         */
 
 /* bits of the replay stream's error flag (scratch word 8B, sl_env_cfg.scratch) */
 #define SL_STREAM_ERR_RANGE 1      /* the supplied stream ran out, or the device
@@ -784,6 +792,14 @@ int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const int32_t *acti
                 const sl_env_cfg *cfg, double *reward, uint8_t *done,
                 uint8_t *info_flags, int32_t *ep_len, int32_t *ep_reward,
                 void *stream);
+
+/* which step kernel family sl_env_step runs for this shape and request:
+   SL_FAMILY_GENERIC, _SMALL_SEG4, _SMALL, _MID, _BITS64, _BITS128; SL_ETOOBIG where
+   kernel == SL_KERNEL_FAST and no bit-sliced kernel takes H x W; SL_EINVAL otherwise bad
+   (host only; no GPU needed).  sl_env_step takes its kernel from this very function; a
+   128x128 state without the goals mirror (sl_env_state.planes) goes to the generic kernel
+   under SL_KERNEL_AUTO and is SL_ETOOBIG under SL_KERNEL_FAST all the same. */
+int sl_env_step_family(int H, int W, int kernel);
 
 /* Complete the uint16 board of every env whose board lives in st->board_planes
  * (SL_POK_BOARD_PLANES without SL_POK_BOARD_FULL): needed before reading st->board directly after

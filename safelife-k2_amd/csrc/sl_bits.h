@@ -1,6 +1,6 @@
 // sl_bits.h -- building blocks of the bit-sliced env-step kernels (sl_bits.hip for
-// 64x64 boards, sl_bits_small.hip for boards up to 32 rows, sl_bits128.hip for 128x128
-// boards): the rule, the scores, the per-env record, and the step phases the kernels
+// 64x64 boards, sl_bits_small.hip for boards up to 32 rows, sl_bits_mid.hip for 33 to 64
+// rows, sl_bits128.hip for 128x128 boards): the rule, the scores, the per-env record, and the step phases the kernels
 // run between them ("shared step phases" at the end).
 //
 // A lane holds two board columns over 32 rows as 16 bit planes x 2 words: plane k,

@@ -1,8 +1,9 @@
 // sl_bits_geo.h -- the geometry policies of rule_planes (sl_bits.h) for the layouts more
 // than one file uses: Geo64 (64x64 boards: sl_bits.hip, sl_rollout_bits.hip), GeoSmall
-// (boards up to 32 rows x 64 columns: sl_bits_small.hip, sl_rollout_bits.hip) and GeoBand
-// with its HaloView (128x128 boards in bands of 32 rows: sl_bits128.hip,
-// sl_rollout_bits128.hip).
+// (boards up to 32 rows x 64 columns: sl_bits_small.hip, sl_rollout_bits.hip), GeoMid
+// (33 to 64 rows, up to 64 columns: sl_bits_mid.hip; here so that the side-effect rollout
+// can take it) and GeoBand with its HaloView (128x128 boards in bands of 32 rows:
+// sl_bits128.hip, sl_rollout_bits128.hip).
 #pragma once
 #include "sl_bits.h"
 
@@ -102,6 +103,82 @@ __device__ __forceinline__ GeoSmall<MODE> small_geo(int lane, int H, int W) {
     g.src_l = active ? (lane == 0 ? nl - 1 : lane - 1) : lane;
     g.src_r = active ? (lane + 1 == nl ? 0 : lane + 1) : lane;
     g.odd_last = (W & 1) && lane == nl - 1;
+    g.src = StreamSrc{nullptr, 0, nullptr};
+    g.pos = 0;
+    g.count = 0;
+    return g;
+}
+
+// Boards of 33 to 64 rows and up to 64 columns: Geo64's split of the rows over lane
+// parity with GeoSmall's columns.  Lane l = 2j + h holds the column pair (2j, 2j+1),
+// j < nl = ceil(W / 2), over rows 32h .. 32h+31: the lower half's 32 rows are all
+// real, the upper half's are its low H - 32 bits (mh), and the bits above them hold
+// no cell: every neighbour word is masked, so they stay clear through the rule.  The
+// rows around a word come from the other half's word (lane l ^ 1) with the torus wrap
+// at H: above row 0 is row H - 1 (the partner's bit H - 33), below row 31 is row 32
+// (its bit 0), above row 32 is row 31 (its bit 31), and below row H - 1 is row 0 (its
+// bit 0, entering at this word's bit H - 33).  At H = 64 this is Geo64's vert_with.
+// Columns come through ds_bpermute from lanes l -+ 2, wrapping at 2 nl; for odd W the
+// last pair's word 1 is a copy of column 0 (GeoSmall).
+template <int MODE>
+struct GeoMid {
+    int lane, H, W, nl;
+    u32 mh;                  // this word's real rows
+    int su;                  // the partner's bit that is the row above this word's row 0
+    int sd;                  // this word's last real row: the partner's bit 0 lies below it
+    int src_l, src_r;        // lanes holding columns 2j - 1 and 2j + 2 of this half
+    bool odd_last;           // this lane's word 1 is the column-0 copy (odd W)
+    StreamSrc src;           // SPAWN_STREAM: the supplied uniforms from this tensor's first
+    int64_t pos;
+    int count;               // SPAWN_COUNT: this lane's eligible cells
+    template <class F>
+    __device__ __forceinline__ V3 vert(const u32 *P, int w, F f) const {
+        const u32 x = f(P, w);
+        const u32 o = lane_x1(x);
+        return V3{((x << 1) | ((o >> su) & 1u)) & mh, ((x >> 1) | ((o & 1u) << sd)) & mh};
+    }
+    __device__ __forceinline__ H3 horiz(u32 w0, u32 w1) const {
+        const u32 right_col = odd_last ? w0 : w1;          // this lane's last real column
+        return H3{(u32)__builtin_amdgcn_ds_bpermute(4 * src_l, (int)right_col),
+                  (u32)__builtin_amdgcn_ds_bpermute(4 * src_r, (int)w0)};
+    }
+    __device__ __forceinline__ bool halo_spawn() const { return false; }
+    // the 2x2 spawn block of rows 32h + y, y + 1 (y even) of the lane's column pair
+    __device__ __forceinline__ u32 block(int y) const {
+        return (u32)(((32 * (lane & 1) + y) >> 1) * nl + (lane >> 1));
+    }
+    // only real cells draw: no row past H - 1, nothing in the column-0 copy (in replay
+    // mode it would shift the real cells' ranks); lanes past the board hold zeros
+    __device__ __forceinline__ void spawn(const u32 elig[2], u32 sp[2], const SpawnCtx &sc,
+                                          u32 tensor) {
+        const u32 e[2] = {elig[0] & mh, odd_last ? 0u : elig[1] & mh};
+        if (MODE == SPAWN_PHILOX) {
+            philox_spawn(*this, e, sp, sc, tensor);
+        } else if (MODE == SPAWN_STREAM) {
+            (void)stream_draws<true>(e, sp, sc.thr, src, pos, lane);
+        } else {
+            count += __builtin_popcount(e[0]) + __builtin_popcount(e[1]);
+        }
+    }
+};
+
+// the geometry of lane `lane` on an H x W board, 33 <= H <= 64 (lanes >= 2 ceil(W / 2)
+// hold nothing)
+template <int MODE>
+__device__ __forceinline__ GeoMid<MODE> mid_geo(int lane, int H, int W) {
+    GeoMid<MODE> g;
+    const int nl = (W + 1) >> 1, h = lane & 1, j = lane >> 1;
+    const bool active = j < nl;
+    g.lane = lane;
+    g.H = H;
+    g.W = W;
+    g.nl = nl;
+    g.mh = (h && H < 64) ? ((1u << (H - 32)) - 1u) : ~0u;
+    g.su = h ? 31 : H - 33;
+    g.sd = h ? H - 33 : 31;
+    g.src_l = active ? (j == 0 ? 2 * (nl - 1) + h : lane - 2) : lane;
+    g.src_r = active ? (j + 1 == nl ? h : lane + 2) : lane;
+    g.odd_last = (W & 1) && j == nl - 1;
     g.src = StreamSrc{nullptr, 0, nullptr};
     g.pos = 0;
     g.count = 0;

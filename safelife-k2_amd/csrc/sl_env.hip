@@ -977,6 +977,25 @@ static void draws_from_ring(StepArgs &a, const sl_mt19937 &mt) {
     }
 }
 
+// Whether SL_KERNEL_AUTO takes the 33-to-64-row kernel where it exists.  Set by the A/B of
+// DESIGN.md 6.3 (profiles/mid_boards_ab.json): at 33x40, 48x48 and 64x48 it is more
+// than twice the per-cell kernel.
+constexpr bool kAutoTakesMid = true;
+
+extern "C" int sl_env_step_family(int H, int W, int kernel) {
+    if (H < 1 || W < 1) return SL_EINVAL;
+    if (kernel != SL_KERNEL_AUTO && kernel != SL_KERNEL_GENERIC && kernel != SL_KERNEL_FAST)
+        return SL_EINVAL;
+    if (kernel != SL_KERNEL_GENERIC) {
+        if (H == 64 && W == 64) return SL_FAMILY_BITS64;
+        if (H == 128 && W == 128) return SL_FAMILY_BITS128;
+        if (small_seg4_shape(H, W)) return SL_FAMILY_SMALL_SEG4;
+        if (small_shape(H, W)) return SL_FAMILY_SMALL;
+        if (mid_shape(H, W) && (kAutoTakesMid || kernel == SL_KERNEL_FAST)) return SL_FAMILY_MID;
+    }
+    return kernel == SL_KERNEL_FAST ? SL_ETOOBIG : SL_FAMILY_GENERIC;
+}
+
 extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const int32_t *actions,
                            const sl_env_cfg *cfg, double *reward, uint8_t *done,
                            uint8_t *info_flags, int32_t *ep_len, int32_t *ep_reward,
@@ -1013,13 +1032,17 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
     if (cfg->stream_phase < 0 || cfg->stream_phase > 2 || (cfg->stream_phase && !replay) ||
         (cfg->stream_phase == 2 && !cfg->stream_base))
         return SL_EINVAL;
-    // (SL_KERNEL_BANDS names a side-effect rollout kernel: no step kernel)
-    if (cfg->kernel == SL_KERNEL_BANDS) return SL_EINVAL;
-    const bool bits_ok = cfg->kernel != SL_KERNEL_GENERIC;
-    const bool fast = bits_ok && st->H == 64 && st->W == 64;
-    const bool fast128 = bits_ok && bits128_shape(*st);
-    const bool small = bits_ok && !fast && small_shape(*st);
-    if (cfg->kernel == SL_KERNEL_FAST && !fast && !fast128 && !small) return SL_ETOOBIG;
+    // the kernel family is sl_env_step_family's answer (SL_KERNEL_BANDS names a
+    // side-effect rollout kernel, no step kernel: SL_EINVAL); `small` stands for every
+    // one-wave kernel with the uint16 board in HBM that resets its own finished envs
+    const int family = sl_env_step_family(st->H, st->W, cfg->kernel);
+    if (family < 0) return family;
+    const bool fast = family == SL_FAMILY_BITS64;
+    // (the 128x128 kernel needs the state's goals mirror as well)
+    const bool fast128 = family == SL_FAMILY_BITS128 && bits128_shape(*st);
+    if (family == SL_FAMILY_BITS128 && !fast128 && cfg->kernel == SL_KERNEL_FAST) return SL_ETOOBIG;
+    const bool mid = family == SL_FAMILY_MID;
+    const bool small = mid || family == SL_FAMILY_SMALL || family == SL_FAMILY_SMALL_SEG4;
     bool reset_done = false;
     FastExtra fx;
     fx.fuse_reset = cfg->auto_reset ? 1 : 0;
@@ -1108,9 +1131,9 @@ extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const in
         if (rc || cfg->stream_phase == 1) return rc;
         reset_done = fx.fuse_reset && fx.pool.K > 0;
     } else if (small) {
-        int rc = launch_step_small(*st, a, fx, actions, cfg->can_toggle_powers,
-                                   cfg->can_toggle_colors, reward, done, info_flags, ep_len,
-                                   ep_reward, s);
+        int rc = (mid ? launch_step_mid : launch_step_small)(
+            *st, a, fx, actions, cfg->can_toggle_powers, cfg->can_toggle_colors, reward, done,
+            info_flags, ep_len, ep_reward, s);
         if (rc || cfg->stream_phase == 1) return rc;
         reset_done = fx.fuse_reset && fx.pool.K > 0 && fx.pool.H == st->H && fx.pool.W == st->W;
     } else if (fast) {

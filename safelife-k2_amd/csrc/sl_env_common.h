@@ -377,6 +377,15 @@ int launch_capture(const sl_env_state &st, const sl_capture &c, const uint8_t *f
 bool bits128_shape(const sl_env_state &st);
 // the bit-sliced kernel for boards up to 32 x 64 (sl_bits_small.hip)
 bool small_shape(const sl_env_state &st);
+bool small_shape(int H, int W);
+// ... of which the shapes that run four envs per wave
+bool small_seg4_shape(int H, int W);
+// the bit-sliced kernel for boards of 33 to 64 rows and up to 64 columns, 64x64 aside
+// (sl_bits_mid.hip); resets as launch_step_small
+bool mid_shape(int H, int W);
+int launch_step_mid(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
+                    const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
+                    uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s);
 // (auto-reset: envs whose episode ended are reset by their own wave from fx.pool)
 int launch_step_small(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
                       const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,

@@ -16,6 +16,12 @@ SL_OK, SL_EINVAL, SL_EHIP, SL_ETOOBIG = 0, -1, -2, -3
 SL_RNG_STREAM, SL_RNG_PHILOX = 0, 1
 SL_KERNEL_AUTO, SL_KERNEL_GENERIC, SL_KERNEL_FAST = 0, 1, 2
 SL_KERNEL_BANDS = 3     # sl_side_effect_densities_k only: the 128x128 four-wave rollout
+# sl_env_step_family: the step kernel family of a board shape and kernel request
+(SL_FAMILY_GENERIC, SL_FAMILY_SMALL_SEG4, SL_FAMILY_SMALL, SL_FAMILY_MID, SL_FAMILY_BITS64,
+ SL_FAMILY_BITS128) = range(6)
+FAMILY_NAMES = {SL_FAMILY_GENERIC: "generic", SL_FAMILY_SMALL_SEG4: "small-seg4",
+                SL_FAMILY_SMALL: "small", SL_FAMILY_MID: "mid", SL_FAMILY_BITS64: "bits64",
+                SL_FAMILY_BITS128: "bits128"}
 SL_STREAM_ERR_RANGE, SL_STREAM_ERR_THRESHOLD = 1, 2
 # sl_emd_cells_device: the size limit of a problem and the negative status codes
 SL_EMD_DEVICE_MAX_CELLS = 256
@@ -134,6 +140,9 @@ def lib():
     L.sl_copy16.argtypes = [vp, vp, i64, vp]
     L.sl_env_step.argtypes = [ctypes.POINTER(EnvState), ctypes.POINTER(LevelPool), vp,
                               ctypes.POINTER(EnvCfg), vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "sl_env_step_family") or LIB_PATH == _DEFAULT_LIB:
+        L.sl_env_step_family.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.sl_env_step_family.restype = ctypes.c_int
     L.sl_env_reset.argtypes = [ctypes.POINTER(EnvState), ctypes.POINTER(LevelPool), vp,
                                ctypes.POINTER(EnvCfg), vp]
     L.sl_level_pool_prepare.argtypes = [ctypes.POINTER(LevelPool), vp]
@@ -208,6 +217,15 @@ def lib():
 def check(rc, what):
     if rc != SL_OK:
         raise RuntimeError("%s failed: %s (code %d)" % (what, _ERRORS.get(rc, "?"), rc))
+
+
+def env_step_family(H, W, kernel=SL_KERNEL_AUTO):
+    """Name of the step kernel family sl_env_step runs on H x W boards for this kernel
+    request (host only); raises where SL_KERNEL_FAST has no bit-sliced kernel."""
+    rc = lib().sl_env_step_family(int(H), int(W), int(kernel))
+    if rc < 0:
+        check(rc, "sl_env_step_family(%d, %d, %d)" % (H, W, kernel))
+    return FAMILY_NAMES[rc]
 
 
 def require_device(device=None):

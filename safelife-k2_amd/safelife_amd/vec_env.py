@@ -228,6 +228,12 @@ class SafeLifeVecEnv:
             raise ValueError("rng must be 'philox' or 'stream'")
         self._bonus_key = None
 
+    @property
+    def kernel_family(self):
+        """Name of the step kernel family this env's steps run (sl_env_step_family):
+        "generic", "small-seg4", "small", "mid", "bits64" or "bits128"."""
+        return _lib.env_step_family(self.H, self.W, self.kernel)
+
     # ------------------------------------------------------------------ setup
     def _alloc(self, obs_dtype):
         torch, dev, B, H, W = self.torch, self.device, self.B, self.H, self.W
