@@ -70,6 +70,11 @@ extern "C" {
                                 SL_ETOOBIG elsewhere.  Accepted by
                                 sl_side_effect_densities_k only
                                 (sl_env_cfg.kernel: SL_EINVAL)                */
+#define SL_KERNEL_MID 4      /* bit-sliced rollout, one wave per board, of boards
+                                of 33 to 64 rows and 2 to 64 columns, 64x64
+                                aside: Philox draws; SL_ETOOBIG elsewhere.
+                                Accepted by sl_side_effect_densities_k only
+                                (sl_env_cfg.kernel: SL_EINVAL)                */
 
 /* the step kernel families of sl_env_step (sl_env_step_family) */
 #define SL_FAMILY_GENERIC 0     /* k_env_action + the per-cell kernel, any shape      */
@@ -309,8 +314,18 @@ int sl_side_effect_densities(const uint16_t *init_board, const uint16_t *final_b
  *            of four waves per board (a wave per band of 32 rows, the band in
  *            registers, one halo row each way through LDS per advance), the same four
  *            launches per call -- Philox draws on 128x128 boards; SL_ETOOBIG elsewhere;
+ *            SL_KERNEL_MID: the bit-sliced rollout of boards of 33 to 64 rows and 2 to 64
+ *            columns, 64x64 aside (the shapes of the mid env step), one wave per board:
+ *            lane 2j + h holds columns 2j, 2j + 1 over rows 32h .. 32h + 31, the same
+ *            four launches per call -- Philox draws on those shapes, read as uint16 (no
+ *            alignment rule); SL_ETOOBIG elsewhere, stream mode included.  SL_KERNEL_FAST
+ *            keeps its shape set and is SL_ETOOBIG on these boards;
  *            SL_KERNEL_AUTO: what sl_side_effect_kernel_auto names: FAST where it
- *            exists, BANDS on 128x128 boards with Philox draws, else GENERIC.
+ *            exists, BANDS on 128x128 boards with Philox draws, else GENERIC.  On the
+ *            MID shapes of at least 32 columns (at least half of the wave's lanes hold
+ *            cells) with Philox draws it names MID, by the measurement of DESIGN.md 6.4
+ *            (one constant, kAutoTakesMidRollout); narrower MID shapes stay on GENERIC
+ *            under AUTO in this version and are served by SL_KERNEL_MID when asked for.
  *            The 64x64 and 128x128 kernels load dwords: such boards at an address that
  *            is no multiple of 4 go to GENERIC under AUTO and are SL_EINVAL under FAST
  *            or BANDS.
@@ -329,8 +344,8 @@ int sl_side_effect_densities_k(const uint16_t *init_board, const uint16_t *final
 /* SL_KERNEL_FAST if SL_KERNEL_AUTO takes the one-wave rollout for such a call, else
  * SL_KERNEL_GENERIC (host only; no GPU needed) */
 int sl_side_effect_kernel(int H, int W, int rng_mode);
-/* the kernel SL_KERNEL_AUTO launches for such a call: SL_KERNEL_GENERIC, SL_KERNEL_FAST
- * or SL_KERNEL_BANDS (host only; no GPU needed; boards the dword loads cannot take,
+/* the kernel SL_KERNEL_AUTO launches for such a call: SL_KERNEL_GENERIC, SL_KERNEL_FAST,
+ * SL_KERNEL_BANDS or SL_KERNEL_MID (host only; no GPU needed; boards the dword loads cannot take,
  * see above, go to GENERIC all the same) */
 int sl_side_effect_kernel_auto(int H, int W, int rng_mode);
 

@@ -471,9 +471,22 @@ extern "C" int sl_side_effect_kernel(int H, int W, int rng_mode) {
 // at E = 1, 64 and 256 the slowest bands run beat the fastest generic run.
 constexpr bool kAutoTakesBands = true;
 
+// Whether SL_KERNEL_AUTO takes the one-wave rollout of 33-to-64-row boards
+// (sl_rollout_bits_mid.hip, Philox) on those of at least kAutoMidMinW columns: there at
+// least half of the wave's lanes hold cells.  Narrower ones stay on the per-cell kernels
+// under AUTO (SL_KERNEL_MID takes them when asked for).  Set by the A/B of DESIGN.md 6.4
+// (profiles/side_effect_rollout_mid_ab.json) by kAutoTakesBands' rule: true if at every
+// measured shape of W >= 32 and every E the slowest mid run beats the fastest generic run.
+// It does: at 33x32, 48x48 and 64x48, E = 1, 64 and 1024 (and at 33x20, measured for the
+// record only).
+constexpr bool kAutoTakesMidRollout = true;
+constexpr int kAutoMidMinW = 32;
+
 extern "C" int sl_side_effect_kernel_auto(int H, int W, int rng_mode) {
     if (rng_mode == SL_RNG_PHILOX && rollout_bands_shape(H, W))
         return kAutoTakesBands ? SL_KERNEL_BANDS : SL_KERNEL_GENERIC;
+    if (rng_mode == SL_RNG_PHILOX && rollout_mid_shape(H, W) && W >= kAutoMidMinW)
+        return kAutoTakesMidRollout ? SL_KERNEL_MID : SL_KERNEL_GENERIC;
     return sl_side_effect_kernel(H, W, rng_mode);
 }
 
@@ -507,7 +520,7 @@ extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
                                           int64_t workspace_bytes, const uint32_t *env_ids,
                                           int kernel, void *stream) {
     if (kernel != SL_KERNEL_AUTO && kernel != SL_KERNEL_GENERIC && kernel != SL_KERNEL_FAST &&
-        kernel != SL_KERNEL_BANDS)
+        kernel != SL_KERNEL_BANDS && kernel != SL_KERNEL_MID)
         return SL_EINVAL;
     if (E < 0 || H < 2 || W < 2 || num_samples < 1 || max_keys < 1 || max_keys > 1024)
         return SL_EINVAL;
@@ -534,6 +547,12 @@ extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
                   (kernel == SL_KERNEL_AUTO &&
                    sl_side_effect_kernel_auto(H, W, rng_mode) == SL_KERNEL_BANDS));
     if (kernel == SL_KERNEL_BANDS && !bands) return SL_ETOOBIG;
+    // ... and the one-wave rollout of 33-to-64-row boards: Philox draws, uint16 reads
+    const bool mid = rng_mode == SL_RNG_PHILOX && rollout_mid_shape(H, W) &&
+                     (kernel == SL_KERNEL_MID ||
+                      (kernel == SL_KERNEL_AUTO &&
+                       sl_side_effect_kernel_auto(H, W, rng_mode) == SL_KERNEL_MID));
+    if (kernel == SL_KERNEL_MID && !mid) return SL_ETOOBIG;
     if (((fast && H == 64) || bands) &&
         ((((uintptr_t)init_board) | ((uintptr_t)final_board)) & 3)) {
         if (kernel != SL_KERNEL_AUTO) return SL_EINVAL;
@@ -553,11 +572,12 @@ extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
         max_steps = num_steps_host[e] > max_steps ? num_steps_host[e] : max_steps;
     }
     const int64_t map_elems = E * (int64_t)max_keys * hw;
-    if (fast || bands) {
+    if (fast || bands || mid) {
         // four launches: mark, compact, count, normalise (sl_rollout_bits.hip,
-        // sl_rollout_bits128.hip); the mark pass writes every bitmap word, the boards stay
-        // where the caller has them
-        const auto launch_rollout = bands ? launch_rollout_bands : launch_rollout_bits;
+        // sl_rollout_bits_mid.hip, sl_rollout_bits128.hip); the mark pass writes every
+        // bitmap word, the boards stay where the caller has them
+        const auto launch_rollout = bands ? launch_rollout_bands
+                                    : mid ? launch_rollout_mid : launch_rollout_bits;
         RolloutArgs ra{init_board, final_board, num_steps_dev, spawn_prob, env_ids, env0, seed,
                        num_samples, H, W, bitmap, keys, n_keys, max_keys, inaction, action};
         if (hipMemsetAsync(inaction, 0, map_elems * 8, s) != hipSuccess ||

@@ -1,5 +1,5 @@
 // sl_rollout_bits.h -- launcher of the bit-sliced side-effect rollout kernels
-// (sl_rollout_bits.hip, sl_rollout_bits128.hip), called by sl_side_effect_densities_k
+// (sl_rollout_bits.hip, sl_rollout_bits_mid.hip, sl_rollout_bits128.hip), called by sl_side_effect_densities_k
 // (sl_board.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,5 +36,13 @@ bool rollout_bands_shape(int H, int W);
 // the same two passes, one launch of 2E four-wave workgroups each; the boards are read
 // as dwords (4-byte aligned)
 int launch_rollout_bands(const RolloutArgs &a, int64_t E, int pass, hipStream_t s);
+
+// the one-wave rollout of boards of 33 to 64 rows (sl_rollout_bits_mid.hip) exists for
+// this shape: 33 <= H <= 64, 2 <= W <= 64, not 64x64 (mid_shape's range), Philox draws only
+bool rollout_mid_shape(int H, int W);
+
+// the same two passes, one launch of 2E single-wave workgroups each; the boards are read
+// as uint16 (no alignment rule)
+int launch_rollout_mid(const RolloutArgs &a, int64_t E, int pass, hipStream_t s);
 
 }  // namespace sl

@@ -16,6 +16,7 @@ SL_OK, SL_EINVAL, SL_EHIP, SL_ETOOBIG = 0, -1, -2, -3
 SL_RNG_STREAM, SL_RNG_PHILOX = 0, 1
 SL_KERNEL_AUTO, SL_KERNEL_GENERIC, SL_KERNEL_FAST = 0, 1, 2
 SL_KERNEL_BANDS = 3     # sl_side_effect_densities_k only: the 128x128 four-wave rollout
+SL_KERNEL_MID = 4       # sl_side_effect_densities_k only: the one-wave rollout of 33 to 64 rows
 # sl_env_step_family: the step kernel family of a board shape and kernel request
 (SL_FAMILY_GENERIC, SL_FAMILY_SMALL_SEG4, SL_FAMILY_SMALL, SL_FAMILY_MID, SL_FAMILY_BITS64,
  SL_FAMILY_BITS128) = range(6)

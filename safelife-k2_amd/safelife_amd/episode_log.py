@@ -100,6 +100,9 @@ class EpisodeLog:
     emd: 'host' solves the EMDs with ``sl_emd_cells_batch``; 'device' (with
     scoring='device' only) solves them where their cells are
     (``side_effect_scores(..., emd="device")``): the same bits.
+    rollout_kw: further keywords of the rollout (``side_effect_densities``), such as
+    ``kernel`` ('auto', 'generic', 'fast', 'bands', or 'mid' for boards of 33 to 64 rows)
+    and ``max_keys``; rng, seed, env_ids and device are the log's own.
     """
 
     _FIELDS = (("score", "int32"), ("possible", "int32"), ("baseline", "int32"),
@@ -109,7 +112,7 @@ class EpisodeLog:
 
     def __init__(self, venv, log_file=None, record_side_effects=True, num_samples=1000,
                  side_effect_seed=0, level_titles=None, other_episode_data=None, ring=64,
-                 scoring="host", emd="host"):
+                 scoring="host", emd="host", rollout_kw=None):
         if scoring not in ("host", "device"):
             raise ValueError("scoring must be 'host' or 'device', not %r" % (scoring,))
         if emd not in ("host", "device"):
@@ -136,6 +139,10 @@ class EpisodeLog:
         self.R = R
         self.scoring = scoring
         self.emd = emd
+        self.rollout_kw = dict(rollout_kw or {})
+        taken = set(self.rollout_kw) & {"rng", "seed", "env_ids", "device", "problems", "emd"}
+        if taken:
+            raise ValueError("rollout_kw may not set %s" % ", ".join(sorted(taken)))
         self._ids = torch.arange(B, dtype=torch.int32, device=dev)
         self._board = torch.zeros((R, B, H, W), dtype=torch.uint16, device=dev)
         self._start = torch.zeros((R, B, H, W), dtype=torch.uint16, device=dev)
@@ -224,7 +231,7 @@ class EpisodeLog:
                                         self.num_samples, rng="philox",
                                         seed=self.side_effect_seed, env_ids=gids,
                                         device=v.device, problems=self.scoring,
-                                        emd=self.emd)
+                                        emd=self.emd, **self.rollout_kw)
         step_count = v.global_counter.num_steps
         other = {k: float(val(step_count) if callable(val) else val)
                  for k, val in self.other_episode_data.items()}

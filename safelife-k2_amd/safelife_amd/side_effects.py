@@ -66,7 +66,8 @@ def _rollout_device(init_boards, final_boards, num_steps, spawn_prob, num_sample
                          device=dev)
     mode = {"philox": _lib.SL_RNG_PHILOX, "stream": _lib.SL_RNG_STREAM}[rng]
     kern = {"auto": _lib.SL_KERNEL_AUTO, "generic": _lib.SL_KERNEL_GENERIC,
-            "fast": _lib.SL_KERNEL_FAST, "bands": _lib.SL_KERNEL_BANDS}[kernel]
+            "fast": _lib.SL_KERNEL_FAST, "bands": _lib.SL_KERNEL_BANDS,
+            "mid": _lib.SL_KERNEL_MID}[kernel]
     ids = None
     if env_ids is not None:
         ids_h = np.ascontiguousarray(np.asarray(env_ids, dtype=np.int64).reshape(-1))
@@ -121,9 +122,13 @@ def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_
     call: Philox draws on 64x64 boards and boards of H <= 32, W <= 64; raises elsewhere),
     'bands' the bit-sliced rollout of 128x128 boards (four waves per board, one per band
     of 32 rows, the same four launches: Philox draws on 128x128 boards; raises elsewhere),
+    'mid' the bit-sliced rollout of boards of 33 to 64 rows and 2 to 64 columns, 64x64
+    aside (one wave per board, the same four launches: Philox draws on those shapes; raises
+    elsewhere; 'fast' still raises on them),
     'generic' the per-cell kernels (one launch per advance), 'auto' takes 'fast' or 'bands'
-    where they exist (``sl_side_effect_kernel_auto`` names the choice).  All give the same
-    bytes.
+    where they exist and 'mid' on its shapes of at least 32 columns
+    (``sl_side_effect_kernel_auto`` names the choice; narrower 'mid' shapes stay on
+    'generic' unless 'mid' is asked for).  All give the same bytes.
     env_ids: [E] Philox env ids, one per episode (default env0 + e), so an episode draws
     the same whatever batch it is scored in.
     Returns a list of (inaction, action) dicts, one per episode.
@@ -382,7 +387,8 @@ def _problems_host(init_boards, final_boards, num_steps, spawn_prob, num_samples
 def side_effect_problems(init_boards, final_boards, num_steps, spawn_prob, num_samples=1000,
                          **rollout_kw):
     """The inputs of ``side_effect_scores``' EMDs, selected on the device: the rollout of
-    ``side_effect_densities`` (``rollout_kw``: rng, seed, env_ids, kernel, max_keys, ...),
+    ``side_effect_densities`` (``rollout_kw``: rng, seed, env_ids, kernel ('auto', 'generic',
+    'fast', 'bands', 'mid'), max_keys, ...),
     then per episode and key the cells ``earth_mover_distance`` would keep of the two
     density maps (side_effects.py:36-43) -- |a - b| > 1e-3 * max |a - b|, row-major -- cut
     out by ``sl_side_effect_problem_counts`` / ``_cells``.  Only those cells, their keys
@@ -491,7 +497,8 @@ def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_sam
                        include=None, exclude=None, problems="host", emd="host", **rollout_kw):
     """side_effects.py:95-161 for E finished episodes: one device call for all rollouts
     (``side_effect_densities``; ``rollout_kw`` goes to it: rng, seed, env_ids, kernel
-    ('auto', 'generic', 'fast', 'bands'), ...), then the host EMD per episode and key.
+    ('auto', 'generic', 'fast', 'bands', 'mid'), ...), then the host EMD per episode and
+    key.
     problems: 'host' copies the dense maps to the host and selects each EMD's cells there
     with numpy; 'device' selects them on the device (``side_effect_problems``), copies only
     those cells and solves all EMDs in one ``sl_emd_cells_batch`` call on
@@ -531,7 +538,8 @@ def side_effect_score(game, num_samples=1000, include=None, exclude=None, proble
     """side_effects.py:95-161 for one game-like object (``_init_data['board']``,
     ``board``, ``num_steps``, ``spawn_prob``): {key: [emd, sum(inaction density)]}.
     The rollout runs on the GPU (``side_effect_densities``); ``kw`` selects its RNG and
-    its kernel ('auto', 'generic', 'fast', or 'bands' for 128x128 boards); ``problems``
+    its kernel ('auto', 'generic', 'fast', 'bands' for 128x128 boards, or 'mid' for boards
+    of 33 to 64 rows); ``problems``
     ('host', 'device') where the EMDs' cells are selected and ``emd`` ('host', 'device')
     where they are solved (``side_effect_scores``).
     The E = 1 case of ``side_effect_scores``."""

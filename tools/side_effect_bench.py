@@ -1,15 +1,22 @@
 #!/usr/bin/env python3
 """A/B of the side-effect rollout kernels: side_effects.side_effect_densities with
 kernel="generic" (one per-cell launch per advance) against the bit-sliced rollout (four
-launches per call): kernel="fast" (one wave per board) or, on 128x128 boards,
-kernel="bands" (four waves per board).
+launches per call): kernel="fast" (one wave per board), on 128x128 boards kernel="bands"
+(four waves per board), or on boards of 33 to 64 rows kernel="mid" (one wave per board).
 
     python tools/side_effect_bench.py [--out profiles/side_effect_rollout_ab.json]
     python tools/side_effect_bench.py --boards 128 [--out profiles/side_effect_rollout128_ab.json]
+    python tools/side_effect_bench.py --boards mid [--out profiles/side_effect_rollout_mid_ab.json]
 
 Default: the C3 pool's 64x64 boards and the C2 pool's 25x25 boards (tests/golden/pools),
 E in {1, 64, 1024} episodes, generic against fast.  --boards 128: the C5 pool's 128x128
 boards, E in {1, 64, 256} (at 256 the maps are already 1 GiB), generic against bands.
+--boards mid: boards of 33x32 (the narrowest SL_KERNEL_AUTO would take), 48x48, 64x48 and
+-- for the record only -- 33x20, E in {1, 64, 1024}, generic against mid; no pool of these
+shapes is committed, so the boards are those of tools/mid_bench.py's seeded generator
+(make_levels).  The record also says what kAutoTakesMidRollout (sl_board.hip) follows from
+it: true if at every shape of W >= 32 and every E the slowest mid run beats the fastest
+generic run.
 num_steps = 1000, num_samples = 1000, max_keys = 16 (at 64 the 64x64
 maps of 1024 episodes are 4 GiB).  Three runs of each kernel, interleaved (generic, fast,
 generic, ...); every timed call runs in a child process of its own under a time limit,
@@ -66,11 +73,16 @@ sys.path.insert(0, os.path.join(REPO, "safelife-k2_amd"))
 
 POOLS = {"c3_64x64": "c3_prune_still_64.npz", "c2_25x25": "c2_append_still_25.npz",
          "c5_128x128": "c5_navigation_128.npz"}
+# generated boards (tools/mid_bench.py: make_levels), by shape
+MID_SHAPES = {"mid_33x32": (33, 32), "mid_48x48": (48, 48), "mid_64x48": (64, 48),
+              "mid_33x20": (33, 20)}
+AUTO_MID_MIN_W = 32         # kAutoMidMinW (sl_board.hip)
 STEPS = SAMPLES = 1000
 MAX_KEYS = 16
 # --boards: the pools, the episode counts, the kernel set against generic, the record
 SETS = {"64": (("c3_64x64", "c2_25x25"), (1, 64, 1024), "fast", "side_effect_rollout_ab.json"),
-        "128": (("c5_128x128",), (1, 64, 256), "bands", "side_effect_rollout128_ab.json")}
+        "128": (("c5_128x128",), (1, 64, 256), "bands", "side_effect_rollout128_ab.json"),
+        "mid": (tuple(MID_SHAPES), (1, 64, 1024), "mid", "side_effect_rollout_mid_ab.json")}
 RUNS = 3
 CALL_LIMIT_S = 240
 # --problems: pool, episode counts, what is timed by default
@@ -82,11 +94,20 @@ EMD_SET = (("c3_64x64", "c2_25x25"), (1, 64, 1024))
 EMD_RECORD = "side_effect_emd_ab.json"
 
 
+def _pool_boards(pool):
+    import numpy as np
+    if pool in MID_SHAPES:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from mid_bench import make_levels
+        return np.stack([d["board"] for d in make_levels(*MID_SHAPES[pool])])
+    return np.load(os.path.join(REPO, "tests", "golden", "pools", POOLS[pool]))["board"]
+
+
 def one_call(pool, E, kernel):
     import numpy as np
     import torch
     from safelife_amd.side_effects import side_effect_densities
-    board = np.load(os.path.join(REPO, "tests", "golden", "pools", POOLS[pool]))["board"]
+    board = _pool_boards(pool)
     init = np.ascontiguousarray(board[np.arange(E) % len(board)])
     final = np.roll(init, 1, axis=2)
     dev = torch.device("cuda:0")
@@ -384,6 +405,13 @@ def main():
             case["speedup_worst_%s_vs_best_generic" % new] = min(case["generic"]) / max(case[new])
             print(json.dumps(case), flush=True)
             result["cases"].append(case)
+    if args.boards == "mid":
+        lost = ["%s E=%d" % (c["pool"], c["E"]) for c in result["cases"]
+                if MID_SHAPES[c["pool"]][1] >= AUTO_MID_MIN_W and not c["mid_wins"]]
+        result["boards"] = "tools/mid_bench.py make_levels(H, W), 32 levels, seed 0"
+        result["auto_min_w"] = AUTO_MID_MIN_W
+        result["auto_takes_mid"] = not lost
+        result["auto_cases_lost"] = lost
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
         json.dump(result, f, indent=1)
