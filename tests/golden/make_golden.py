@@ -31,9 +31,12 @@ Fixtures and synthetic level pools (§8(d)):
                                  levels with several exits, toggles on, other bonus
                                  periods and views (group "feat"; levels built by
                                  tests/feature_pools.py, stored in the fixture)
+  obs_views.npz                  G9: SafeLifeEnv.get_obs of explicit small states (group
+                                 "obs"; states built by tests/obs_cases.py, stored in the
+                                 fixture)
 
 Usage: python tests/golden/make_golden.py [--only g1,g2,traj,dens,pools,pool128,
-                                                  g1_128,g2_128,traj128,g7,feat]
+                                                  g1_128,g2_128,traj128,g7,feat,obs]
 """
 import argparse
 import hashlib
@@ -571,6 +574,57 @@ def gen_dens(out):
     print("G5 ->", out)
 
 
+def gen_obs(out):
+    """G9: SafeLifeEnv.get_obs (safelife_env.py:125-155) through recenter_view
+    (helper_utils.py:41-74) of the explicit states of tests/obs_cases.py (FIXTURE_SPECS):
+    views of several times the board, single-row and even views, 0 to 8 exits in list
+    order, exits stacked on one border cell, in the view corners and at wrapped distance
+    exactly H/2.  The env gets a game that holds just what get_obs reads: board, goals,
+    agent_loc and exit_locs (the exit list as np.nonzero would return it, two index
+    arrays), so the list need not match the board's exit bits.  A state the reference
+    raises on would be left out; it raises on none."""
+    from types import SimpleNamespace
+    from safelife.safelife_env import SafeLifeEnv
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    import obs_cases
+    rec = {k: [] for k in ("shape", "view", "agent_loc", "remove_white", "channels", "exit_count",
+                           "exits", "board", "goals", "obs")}
+    for i, s in enumerate(obs_cases.fixture_states()):
+        env = SafeLifeEnv(iter(()), view_shape=tuple(s["view"]),
+                          remove_white_goals=s["remove_white"], output_channels=s["channels"])
+        ex = np.array(s["exits"], dtype=np.int64).reshape(-1, 2)
+        env.game = SimpleNamespace(board=s["board"].copy(), goals=s["goals"].copy(),
+                                   agent_loc=(s["ax"], s["ay"]), exit_locs=(ex[:, 0], ex[:, 1]))
+        try:
+            obs = np.asarray(env.get_obs())
+        except Exception as e:                       # noqa: BLE001 -- reported, state dropped
+            print("G9 state", i, "raises in the reference:", repr(e))
+            continue
+        assert np.array_equal(env.game.board, s["board"])        # get_obs works on a copy
+        chans = list(s["channels"] or ())
+        assert obs.shape == tuple(s["view"]) + ((len(chans),) if chans else ())
+        assert np.array_equal(obs.astype(np.uint16), obs)
+        rec["shape"].append(s["board"].shape)
+        rec["view"].append(s["view"])
+        rec["agent_loc"].append((s["ax"], s["ay"]))
+        rec["remove_white"].append(bool(s["remove_white"]))
+        rec["channels"].append(chans + [-1] * (16 - len(chans)))
+        rec["exit_count"].append(len(ex))
+        rec["exits"].append(np.concatenate([ex, np.full((8 - len(ex), 2), -1)]))
+        rec["board"].append(s["board"].ravel())
+        rec["goals"].append(s["goals"].ravel())
+        rec["obs"].append(obs.astype(np.uint16).ravel())
+    # one array per field: every state's cells end to end, in state order
+    out_rec = {k: np.array(rec[k], np.int16) for k in ("shape", "view", "agent_loc", "channels",
+                                                       "exit_count", "exits")}
+    out_rec["remove_white"] = np.array(rec["remove_white"])
+    for k in ("board", "goals", "obs"):
+        out_rec[k] = np.concatenate(rec[k]).astype(np.uint16)
+    np.savez_compressed(out, **out_rec)
+    print("G9", len(rec["view"]), "states ->", out, os.path.getsize(out), "bytes")
+
+
 # ----------------------------------------------------------------------------
 POOL_SPECS = {
     # name: (yaml, board_shape, K)
@@ -666,6 +720,8 @@ def main():
     if "feat" in only:
         for name, src, kw in FEAT_SPECS:
             run_traj(name, src, prefix="feat_", **kw)
+    if "obs" in only:
+        gen_obs(os.path.join(HERE, "obs_views.npz"))
 
 
 if __name__ == "__main__":
