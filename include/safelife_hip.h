@@ -816,6 +816,58 @@ int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const int32_t *acti
    under SL_KERNEL_AUTO and is SL_ETOOBIG under SL_KERNEL_FAST all the same. */
 int sl_env_step_family(int H, int W, int kernel);
 
+/* sl_step_plan.obs: who writes the step's views */
+#define SL_PLAN_OBS_NONE 0
+#define SL_PLAN_OBS_FUSED64 1    /* the 64x64 step kernel (and its reset list)          */
+#define SL_PLAN_OBS_FUSED128 2   /* the 128x128 step kernel, then the reset envs' views */
+#define SL_PLAN_OBS_SEPARATE 3   /* the observation kernel over all envs, after resets  */
+/* sl_step_plan.resets: who resets the finished envs */
+#define SL_PLAN_RESETS_NONE 0
+#define SL_PLAN_RESETS_IN_KERNEL 1   /* the small / mid step kernel, each wave its own   */
+#define SL_PLAN_RESETS_LIST64 2      /* k_env_reset_list over the step kernel's list     */
+#define SL_PLAN_RESETS_SPLIT_TAIL64 3 /* k_env_epilogue_reset64 after k_env_planes64_s6  */
+#define SL_PLAN_RESETS_LIST128 4     /* k_env_reset_list_wide over the step kernel's list */
+#define SL_PLAN_RESETS_SCAN 5        /* k_env_reset_scan over the step's flags           */
+/* sl_step_plan.kernel64: the 64x64 instance family (0 for every other family) */
+#define SL_PLAN_K64_NONE 0
+#define SL_PLAN_K64_BITS64 1   /* k_env_step_bits64<view_kind, spawn mode>               */
+#define SL_PLAN_K64_PLANES 2   /* k_env_step_bits64_planes<keep, view_kind>              */
+#define SL_PLAN_K64_GRAY 3     /* k_env_planes64_gray<C3, view_kind>                     */
+#define SL_PLAN_K64_W6 4       /* k_env_planes64_w6<C3>                                  */
+#define SL_PLAN_K64_S6 5       /* k_env_planes64_s6<C3>, then the split tail             */
+#define SL_PLAN_K64_CHAN 6     /* k_env_planes64_chan<keep, element size of view_kind>   */
+/* sl_step_plan.keep: the plane instances' class of kept board planes */
+#define SL_PLAN_KEEP_RUNTIME 0 /* from board_zero / agent_planes at run time             */
+#define SL_PLAN_KEEP_C3 1      /* planes 0x877F with agent planes 0x0062, compiled in    */
+#define SL_PLAN_KEEP_ALL 2     /* all sixteen                                            */
+
+/* What sl_env_step would run for this state, pool, cfg and info_flags: every decision it
+ * takes before its first launch.  Host only; no GPU needed, nothing is launched and no
+ * device pointer is read (sl_env_step itself runs from this plan). */
+typedef struct sl_step_plan {
+    int32_t empty;          /* 1: the state holds no env; nothing runs, nothing else is set */
+    int32_t family;         /* SL_FAMILY_*: sl_env_step_family's answer, or generic for a
+                               128x128 state without the goals mirror                     */
+    int32_t replay;         /* SL_RNG_STREAM                                              */
+    int32_t stream_phase;   /* sl_env_cfg.stream_phase                                    */
+    int32_t plane_mode;     /* the step keeps the board in sl_env_state.board_planes      */
+    int32_t demote_first;   /* boards in planes are completed and the planes marked stale
+                               before the step                                            */
+    int32_t obs;            /* SL_PLAN_OBS_*                                              */
+    int32_t resets;         /* SL_PLAN_RESETS_*                                           */
+    int32_t capture;        /* 1: sl_env_cfg.capture is taken (small / mid resets then move
+                               to the scan, after the first frame)                        */
+    int32_t kernel64;       /* SL_PLAN_K64_*                                              */
+    int32_t keep;           /* SL_PLAN_KEEP_* (kernel64 PLANES, GRAY, W6, S6, CHAN)       */
+    int32_t view_kind;      /* views the step kernel writes: 0 none, 1 packed, 2 u16 / bf16
+                               channels, 3 u8 channels, 4 f32 channels                    */
+} sl_step_plan;
+
+/* Same return codes as sl_env_step for anything it rejects before launching
+ * (actions, reward and done aside, which the plan does not need). */
+int sl_env_step_plan(const sl_env_state *st, const sl_level_pool *pool, const sl_env_cfg *cfg,
+                     const uint8_t *info_flags, sl_step_plan *out);
+
 /* Complete the uint16 board of every env whose board lives in st->board_planes
  * (SL_POK_BOARD_PLANES without SL_POK_BOARD_FULL): needed before reading st->board directly after
  * steps that kept the board in planes.  No-op without board_planes. */

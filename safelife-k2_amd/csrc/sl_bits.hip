@@ -30,7 +30,7 @@
 // kernel carries no reset code (128 VGPRs, 4 waves/SIMD, no spills).  The <true>
 // instantiation also writes the packed observation (write_obs, 130 VGPRs, 3 waves).
 #include "sl_bits_geo.h"
-#include "sl_obs.h"
+#include "sl_env_step.h"
 
 using namespace sl;
 using namespace sl::fast;
@@ -882,7 +882,6 @@ k_env_step_bits64(StepKArgs ka) {
 // the instantiations: every plane, the C3 / C4 pools' planes (cell bits 0-6, 8-10, 15,
 // of which the agent's 1, 5, 6 are implied), and any other masks at run time
 constexpr u32 kKeepAll = 0xFFFFu, kKeepC3 = 0x877Fu, kAgentC3 = 0x0062u;
-constexpr u32 kKeepC3Fixed = 0x10000u | kKeepC3;   // the dispatch's: kKeepC3 with kAgentC3
 template <u32 K16>       // the held planes, fixed at compile time; 0: from board_zero
 struct PlaneSlots {
     // kKeepC3 fixes the agent planes too (the dispatch checks both); the other two
@@ -1030,7 +1029,7 @@ k_env_planes64_w6(StepKArgs ka) {
 // k_env_planes64_w6 without its one-lane tail: after the plane stores lane 0 writes the
 // env's hand-over record (Handover, sl_bits.h) and the wave ends; the epilogue and the
 // resets run in k_env_epilogue_reset64 below, launched right after.  Same registers and
-// buffer; launched only with auto-reset from a pool (launch_step_bits).  (Named apart from
+// buffer; launched only with auto-reset from a pool (SL_PLAN_K64_S6).  (Named apart from
 // k_env_planes64_w6, whose resource test counts by name;
 // tests/test_kernel_resources_split.py.)
 template <u32 K16>
@@ -1227,17 +1226,6 @@ k_env_reset_list(sl_env_state st, sl_level_pool pool, ResetArgs ra, int64_t *scr
     }
 }
 
-// the step kernel's view mode for fx (k_env_step_bits64's OBS)
-int obs_kind(const FastExtra &fx) {
-    if (!fx.obs_out) return 0;
-    switch (fx.obs_mode) {
-    case SL_OBS_PACKED: return 1;
-    case SL_OBS_CHANNELS_U8: return 3;
-    case SL_OBS_CHANNELS_F32: return 4;
-    default: return 2;               // u16 and bf16 channels
-    }
-}
-
 template <int MODE>
 void launch_bits64(int kind, unsigned grid, const StepKArgs &ka, hipStream_t s) {
     switch (kind) {
@@ -1258,11 +1246,93 @@ void launch_planes64_chan_k(int esz, unsigned grid, const StepKArgs &ka, hipStre
     }
 }
 
-// the plane kernel with channel views: by the kept planes and the element size
-void launch_planes64_chan(u32 keep, int esz, unsigned grid, const StepKArgs &ka, hipStream_t s) {
-    if (keep == kKeepC3Fixed) launch_planes64_chan_k<kKeepC3>(esz, grid, ka, s);
-    else if (keep == kKeepAll) launch_planes64_chan_k<kKeepAll>(esz, grid, ka, s);
-    else launch_planes64_chan_k<0>(esz, grid, ka, s);
+// the plane kernel with channel views: by the keep class (SL_PLAN_KEEP_*) and element size
+void launch_planes64_chan(int keep, int esz, unsigned grid, const StepKArgs &ka, hipStream_t s) {
+    switch (keep) {
+    case SL_PLAN_KEEP_C3: launch_planes64_chan_k<kKeepC3>(esz, grid, ka, s); break;
+    case SL_PLAN_KEEP_ALL: launch_planes64_chan_k<kKeepAll>(esz, grid, ka, s); break;
+    default: launch_planes64_chan_k<0>(esz, grid, ka, s); break;
+    }
+}
+
+template <u32 K16>
+void launch_planes64_k(int obs, unsigned grid, const StepKArgs &ka, hipStream_t s) {
+    if (obs)
+        hipLaunchKernelGGL((k_env_step_bits64_planes<K16, 1>), dim3(grid), dim3(64), 0, s, ka);
+    else
+        hipLaunchKernelGGL((k_env_step_bits64_planes<K16, 0>), dim3(grid), dim3(64), 0, s, ka);
+}
+
+// the plane kernel without views or with packed ones
+void launch_planes64(int keep, int obs, unsigned grid, const StepKArgs &ka, hipStream_t s) {
+    switch (keep) {
+    case SL_PLAN_KEEP_C3: launch_planes64_k<kKeepC3>(obs, grid, ka, s); break;
+    case SL_PLAN_KEEP_ALL: launch_planes64_k<kKeepAll>(obs, grid, ka, s); break;
+    default: launch_planes64_k<0>(obs, grid, ka, s); break;
+    }
+}
+
+StepKArgs kargs_of(const StepCall &c) {
+    return StepKArgs{*c.st, c.a, c.fx, c.actions, c.ctp, c.ctc, c.reward, c.done, c.flags,
+                     c.ep_len, c.ep_rew};
+}
+
+// replay: the actions (k_env_action, one lane per env), then each env's eligible counts
+int counts64(const StepCall &c) {
+    const sl_env_state &st = *c.st;
+    const int rc = launch_env_action(st, c.actions, c.ctp, c.ctc,
+                                     scratch_of(c.fx.scratch, st.B).act, c.s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_stream_prologue64, dim3((unsigned)st.B), dim3(64), 0, c.s, kargs_of(c));
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+
+// the step kernel: the instance the plan names
+int step64(const StepCall &c) {
+    const StepPlan &p = c.plan;
+    const unsigned grid = (unsigned)c.st->B;
+    const StepKArgs ka = kargs_of(c);
+    hipStream_t s = c.s;
+    switch (p.kernel64) {
+    case SL_PLAN_K64_BITS64:
+        if (p.replay) launch_bits64<SPAWN_STREAM>(p.view_kind, grid, ka, s);
+        else launch_bits64<SPAWN_PHILOX>(p.view_kind, grid, ka, s);
+        break;
+    case SL_PLAN_K64_PLANES: launch_planes64(p.keep, p.view_kind, grid, ka, s); break;
+    case SL_PLAN_K64_CHAN: launch_planes64_chan(p.keep, obs_esz(p.view_kind), grid, ka, s); break;
+    case SL_PLAN_K64_GRAY:       // goals all black or white: the instances that skip their colours
+        if (p.view_kind)
+            hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 1>), dim3(grid), dim3(64), 0, s, ka);
+        else                     // (sl_env_cfg.planes64_waves 5: the five-wave twin)
+            hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 0>), dim3(grid), dim3(64), 0, s, ka);
+        break;
+    case SL_PLAN_K64_S6:
+        hipLaunchKernelGGL((k_env_planes64_s6<kKeepC3>), dim3(grid), dim3(64), 0, s, ka);
+        break;
+    case SL_PLAN_K64_W6:
+        hipLaunchKernelGGL((k_env_planes64_w6<kKeepC3>), dim3(grid), dim3(64), 0, s, ka);
+        break;
+    default: return SL_EINVAL;
+    }
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+
+// the finished envs: the split pair's tail (the epilogue of every env, then the resets),
+// or the resets of the envs the step kernel listed, with their views
+int resets64(const StepCall &c) {
+    const sl_env_state &st = *c.st;
+    const FastExtra &fx = c.fx;
+    if (c.plan.resets == SL_PLAN_RESETS_SPLIT_TAIL64) {
+        const unsigned tgrid = (unsigned)((st.B + kTailThreads - 1) / kTailThreads);
+        hipLaunchKernelGGL(k_env_epilogue_reset64, dim3(tgrid), dim3(kTailThreads), 0, c.s, st, c.a,
+                           fx.pool, fx.ra, fx.scratch, c.reward, c.done, c.flags, c.ep_len,
+                           c.ep_rew);
+    } else {
+        const unsigned grid = (unsigned)(st.B < 512 ? st.B : 512);
+        hipLaunchKernelGGL(k_env_reset_list, dim3(grid), dim3(64), 0, c.s, st, fx.pool, fx.ra,
+                           fx.scratch, c.a.step, c.plan.oa, fx.obs_chpack, fx.obs_one, fx.obs_out);
+    }
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }
 
 }  // namespace
@@ -1279,93 +1349,17 @@ int sync_board_planes64(const sl_env_state &st, int demote, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }
 
-int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
-                     const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                     uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s,
-                     int planes64_waves) {
-    if (st.H != N || st.W != N) return SL_ETOOBIG;
-    const unsigned grid = (unsigned)st.B;
-    const StepKArgs ka{st, a, fx, actions, ctp, ctc, reward, done, flags, ep_len, ep_rew};
-    bool split = false;      // the step kernel left the epilogue and the resets to a tail kernel
-    if (fx.obs_out && (fx.obs_vh < 1 || fx.obs_vw < 1 || fx.obs_vh * fx.obs_vw > 4096))
-        return SL_EINVAL;
-    if (fx.stream) {
-        if (stream_counts(fx)) {
-            const int rca = launch_env_action(st, actions, ctp, ctc, scratch_of(fx.scratch, st.B).act, s);
-            if (rca) return rca;
-            hipLaunchKernelGGL(k_stream_prologue64, dim3(grid), dim3(64), 0, s, ka);
-            if (hipGetLastError() != hipSuccess) return SL_EHIP;
-        }
-        const int rc = stream_offsets(st, fx, s);
-        if (rc || !stream_steps(fx)) return rc;
-        if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
-        launch_bits64<SPAWN_STREAM>(obs_kind(fx), grid, ka, s);
-    } else {
-        if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
-        if (fx.plane_mode) {
-            // the <kKeepC3, *> instances fix the agent planes as well: a batch holding
-            // those planes whose agent planes differ takes the run-time instance
-            u32 keep = ~st.board_zero & 0xFFFFu;
-            if (keep == kKeepC3) keep = st.agent_planes == kAgentC3 ? kKeepC3Fixed : 0u;
-            const int kind = obs_kind(fx);
-            // the six-wave kernel's split pair (k_env_planes64_s6 + k_env_epilogue_reset64):
-            // auto-reset from a pool, no views, no capture (its launch must see the flags
-            // before the resets); planes64_waves -6 keeps the epilogue in the wave
-            split = keep == kKeepC3Fixed && st.goals_gray && kind == 0 && planes64_waves != 5 &&
-                    planes64_waves != SL_PLANES64_W6_UNSPLIT && fx.fuse_reset && fx.pool.K > 0 &&
-                    !fx.capture && fx.scratch && (reinterpret_cast<uintptr_t>(fx.scratch) & 15) == 0;
-            if (kind >= 2) {
-                launch_planes64_chan(keep, obs_esz(kind), grid, ka, s);
-            } else if (keep == kKeepC3Fixed && st.goals_gray) {
-                // goals all black or white: the instances that skip their colours
-                if (kind)
-                    hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 1>), dim3(grid), dim3(64), 0, s, ka);
-                else if (planes64_waves == 5)  // (sl_env_cfg.planes64_waves: the five-wave twin)
-                    hipLaunchKernelGGL((k_env_planes64_gray<kKeepC3, 0>), dim3(grid), dim3(64), 0, s, ka);
-                else if (split)
-                    hipLaunchKernelGGL((k_env_planes64_s6<kKeepC3>), dim3(grid), dim3(64), 0, s, ka);
-                else
-                    hipLaunchKernelGGL((k_env_planes64_w6<kKeepC3>), dim3(grid), dim3(64), 0, s, ka);
-            } else if (fx.obs_out) {
-                if (keep == kKeepC3Fixed)
-                    hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepC3, 1>), dim3(grid), dim3(64), 0, s, ka);
-                else if (keep == kKeepAll)
-                    hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepAll, 1>), dim3(grid), dim3(64), 0, s, ka);
-                else
-                    hipLaunchKernelGGL((k_env_step_bits64_planes<0, 1>), dim3(grid), dim3(64), 0, s, ka);
-            } else if (keep == kKeepC3Fixed) {
-                hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepC3, 0>), dim3(grid), dim3(64), 0, s, ka);
-            } else if (keep == kKeepAll) {
-                hipLaunchKernelGGL((k_env_step_bits64_planes<kKeepAll, 0>), dim3(grid), dim3(64), 0, s, ka);
-            } else {
-                hipLaunchKernelGGL((k_env_step_bits64_planes<0, 0>), dim3(grid), dim3(64), 0, s, ka);
-            }
-        }
-        else
-            launch_bits64<SPAWN_PHILOX>(obs_kind(fx), grid, ka, s);
-    }
-    if (hipGetLastError() != hipSuccess) return SL_EHIP;
-    if (fx.ev_end) (void)hipEventRecord((hipEvent_t)fx.ev_end, s);
-    if (fx.capture) {          // the frame before this step's resets
-        const int rc = launch_capture(st, *fx.capture, flags, 0, s);
-        if (rc) return rc;
-    }
-    if (split) {
-        const unsigned tgrid = (unsigned)((st.B + kTailThreads - 1) / kTailThreads);
-        hipLaunchKernelGGL(k_env_epilogue_reset64, dim3(tgrid), dim3(kTailThreads), 0, s, st, a,
-                           fx.pool, fx.ra, fx.scratch, reward, done, flags, ep_len, ep_rew);
-    } else if (fx.fuse_reset && fx.pool.K > 0) {
-        const unsigned grid = (unsigned)(st.B < 512 ? st.B : 512);
-        sl::obs::ObsArgs oa{};
-        oa.vh = fx.obs_vh;
-        oa.vw = fx.obs_vw;
-        oa.remove_white = fx.obs_rw;
-        oa.mode = fx.obs_mode;
-        oa.nch = fx.obs_nch;
-        hipLaunchKernelGGL(k_env_reset_list, dim3(grid), dim3(64), 0, s, st, fx.pool, fx.ra,
-                           fx.scratch, a.step, oa, fx.obs_chpack, fx.obs_one, fx.obs_out);
-    }
-    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+int planes64_keep(const sl_env_state &st) {
+    const u32 keep = ~st.board_zero & 0xFFFFu;
+    // the <kKeepC3, *> instances fix the agent planes as well: a batch holding those
+    // planes whose agent planes differ takes the run-time instance
+    if (keep == kKeepC3) return st.agent_planes == kAgentC3 ? SL_PLAN_KEEP_C3 : SL_PLAN_KEEP_RUNTIME;
+    return keep == kKeepAll ? SL_PLAN_KEEP_ALL : SL_PLAN_KEEP_RUNTIME;
+}
+
+const StepHooks &hooks_64() {
+    static const StepHooks h = {counts64, nullptr, step64, resets64, false};
+    return h;
 }
 
 }  // namespace sl

@@ -39,7 +39,7 @@
 // one 1024-thread block per env).
 #include "sl_bits_geo.h"
 #include "sl_env_action.h"
-#include "sl_obs.h"
+#include "sl_env_step.h"
 
 using namespace sl;
 using namespace sl::fast;
@@ -1421,64 +1421,64 @@ int sync_board_planes(const sl_env_state &st, int demote, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }
 
-int launch_step_bits128(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
-                        const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                        uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s) {
-    if (!bits128_shape(st)) return SL_ETOOBIG;
-    const Step128KArgs ka{st, a, fx, actions, ctp, ctc, reward, done, flags, ep_len, ep_rew};
-    const dim3 grid((unsigned)st.B);
-    if (fx.stream) {
-        if (stream_counts(fx)) {
-            if (fx.plane_mode) {
-                hipLaunchKernelGGL(k_env_action_planes128, dim3((unsigned)((st.B + 255) / 256)),
-                                   dim3(256), 0, s, st, actions, ctp, ctc,
-                                   scratch_of(fx.scratch, st.B).act);
-                if (hipGetLastError() != hipSuccess) return SL_EHIP;
-            } else {
-                const int rca = launch_env_action(st, actions, ctp, ctc, scratch_of(fx.scratch, st.B).act, s);
-                if (rca) return rca;
-            }
-            hipLaunchKernelGGL(k_stream_prologue128, grid, dim3(64), 0, s, ka);
-            if (hipGetLastError() != hipSuccess) return SL_EHIP;
-        }
-        FastExtra fo = fx;
-        fo.thr_checked = stream_counts(fx);     // (in the count prologue)
-        const int rc = stream_offsets(st, fo, s);
-        if (rc || !stream_steps(fx)) return rc;
-        if (st.elig_planes) {       // draws decided up front
-            if (a.draw_bits)
-                hipLaunchKernelGGL(k_stream_draw128_bits, grid, dim3(64), 0, s, ka);
-            else
-                hipLaunchKernelGGL(k_stream_draw128, grid, dim3(64), 0, s, ka);
-            if (hipGetLastError() != hipSuccess) return SL_EHIP;
-            if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
-            launch_step128<SPAWN_DECIDED>(ka, fx.plane_mode && fx.obs_out, s);
-        } else {
-            if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
-            hipLaunchKernelGGL((k_env_step_bits128<SPAWN_STREAM, kKeep128All>), grid, dim3(64), 0, s, ka);
-        }
-    } else {
-        if (fx.plane_mode) {
-            hipLaunchKernelGGL(k_env_action_planes128, dim3((unsigned)((st.B + 255) / 256)),
-                               dim3(256), 0, s, st, actions, ctp, ctc,
-                               scratch_of(fx.scratch, st.B).act);
-            if (hipGetLastError() != hipSuccess) return SL_EHIP;
-        } else {
-            const int rc = launch_env_action(st, actions, ctp, ctc, scratch_of(fx.scratch, st.B).act, s);
-            if (rc) return rc;
-        }
-        if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
-        launch_step128<SPAWN_PHILOX>(ka, fx.plane_mode && fx.obs_out, s);
-    }
-    if (hipGetLastError() != hipSuccess) return SL_EHIP;
-    if (fx.ev_end) (void)hipEventRecord((hipEvent_t)fx.ev_end, s);
-    if (fx.capture) {          // the frame before this step's resets
-        const int rc = launch_capture(st, *fx.capture, flags, 0, s);
-        if (rc) return rc;
-    }
-    if (fx.fuse_reset && fx.pool.K > 0)
-        return launch_reset_list_wide(st, fx.pool, fx.ra, fx.scratch, a.step, s);
-    return SL_OK;
+namespace {
+Step128KArgs kargs_of(const StepCall &c) {
+    return Step128KArgs{*c.st, c.a, c.fx, c.actions, c.ctp, c.ctc, c.reward, c.done, c.flags,
+                        c.ep_len, c.ep_rew};
+}
+
+// the action of every env ahead of the step kernel, one lane each: on the planes' few
+// uint16 rows in plane mode, else k_env_action on the uint16 board
+int action128(const StepCall &c) {
+    const sl_env_state &st = *c.st;
+    int64_t *act = scratch_of(c.fx.scratch, st.B).act;
+    if (!c.fx.plane_mode) return launch_env_action(st, c.actions, c.ctp, c.ctc, act, c.s);
+    hipLaunchKernelGGL(k_env_action_planes128, dim3((unsigned)((st.B + 255) / 256)), dim3(256), 0,
+                       c.s, st, c.actions, c.ctp, c.ctc, act);
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+
+// replay: the actions, then each env's eligible counts (and the bit ring's threshold check)
+int counts128(const StepCall &c) {
+    const int rc = action128(c);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_stream_prologue128, dim3((unsigned)c.st->B), dim3(64), 0, c.s, kargs_of(c));
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+
+// Philox: the actions.  Replay with draw planes: the draws, decided up front
+int pre_step128(const StepCall &c) {
+    if (!c.plan.replay) return action128(c);
+    if (!c.st->elig_planes) return SL_OK;
+    const dim3 grid((unsigned)c.st->B);
+    if (c.a.draw_bits)
+        hipLaunchKernelGGL(k_stream_draw128_bits, grid, dim3(64), 0, c.s, kargs_of(c));
+    else
+        hipLaunchKernelGGL(k_stream_draw128, grid, dim3(64), 0, c.s, kargs_of(c));
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+
+int step128(const StepCall &c) {
+    const Step128KArgs ka = kargs_of(c);
+    const bool views = c.plan.obs == SL_PLAN_OBS_FUSED128;
+    if (!c.plan.replay)
+        launch_step128<SPAWN_PHILOX>(ka, views, c.s);
+    else if (c.st->elig_planes)
+        launch_step128<SPAWN_DECIDED>(ka, views, c.s);
+    else
+        hipLaunchKernelGGL((k_env_step_bits128<SPAWN_STREAM, kKeep128All>), dim3((unsigned)c.st->B),
+                           dim3(64), 0, c.s, ka);
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+
+int resets128(const StepCall &c) {
+    return launch_reset_list_wide(*c.st, c.fx.pool, c.fx.ra, c.fx.scratch, c.a.step, c.s);
+}
+}  // namespace
+
+const StepHooks &hooks_128() {
+    static const StepHooks h = {counts128, pre_step128, step128, resets128, true};
+    return h;
 }
 
 }  // namespace sl

@@ -298,33 +298,33 @@ bool mid_shape(int H, int W) {
     return H >= kMinH && H <= kMaxH && W >= 2 && W <= kMaxW && !(H == 64 && W == 64);
 }
 
-int launch_step_mid(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
-                    const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                    uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s) {
-    if (!mid_shape(st.H, st.W)) return SL_ETOOBIG;
-    if (st.B > 0x7FFFFFFF) return SL_EINVAL;
-    sl_level_pool pool = fx.pool;
-    if (!fx.fuse_reset || pool.H != st.H || pool.W != st.W) pool.K = 0;
-    const SmallKArgs ka{st, a, actions, ctp, ctc, reward, done, flags, ep_len, ep_rew, pool,
-                        fx.ra, fx.scratch};
+namespace {
+// replay: the actions (k_env_action, one lane per env), then each env's eligible counts
+int counts_mid(const StepCall &c) {
+    const sl_env_state &st = *c.st;
+    const int rc = launch_env_action(st, c.actions, c.ctp, c.ctc,
+                                     scratch_of(c.fx.scratch, st.B).act, c.s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_stream_prologue_mid, dim3((unsigned)st.B), dim3(64), 0, c.s,
+                       small_kargs(c));
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+
+int step_mid(const StepCall &c) {
+    const sl_env_state &st = *c.st;
     const size_t lds = (size_t)st.H * 32 * sizeof(uint32_t);
     const dim3 grid((unsigned)st.B);
-    if (fx.stream) {
-        if (stream_counts(fx)) {
-            const int rca = launch_env_action(st, actions, ctp, ctc, scratch_of(fx.scratch, st.B).act, s);
-            if (rca) return rca;
-            hipLaunchKernelGGL(k_stream_prologue_mid, grid, dim3(64), 0, s, ka);
-            if (hipGetLastError() != hipSuccess) return SL_EHIP;
-        }
-        const int rc = stream_offsets(st, fx, s);
-        if (rc || !stream_steps(fx)) return rc;
-        if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
-        hipLaunchKernelGGL(k_env_step_mid<SPAWN_STREAM>, grid, dim3(64), lds, s, ka);
-    } else {
-        if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
-        hipLaunchKernelGGL(k_env_step_mid<SPAWN_PHILOX>, grid, dim3(64), lds, s, ka);
-    }
+    if (c.plan.replay)
+        hipLaunchKernelGGL(k_env_step_mid<SPAWN_STREAM>, grid, dim3(64), lds, c.s, small_kargs(c));
+    else
+        hipLaunchKernelGGL(k_env_step_mid<SPAWN_PHILOX>, grid, dim3(64), lds, c.s, small_kargs(c));
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+}  // namespace
+
+const StepHooks &hooks_mid() {
+    static const StepHooks h = {counts_mid, nullptr, step_mid, reset_scan, false};
+    return h;
 }
 
 }  // namespace sl

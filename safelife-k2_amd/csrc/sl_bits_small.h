@@ -4,6 +4,7 @@
 // reset of a finished env by its own wave.
 #pragma once
 #include "sl_bits_geo.h"
+#include "sl_env_step.h"
 
 namespace sl {
 namespace bits {
@@ -86,6 +87,14 @@ struct SmallKArgs {
     ResetArgs ra;
     int64_t *scratch;         // sl_env_cfg.scratch (replay mode: act, offsets, err)
 };
+
+// a call's arguments; the pool only where the step kernel itself resets finished envs
+inline SmallKArgs small_kargs(const StepCall &c) {
+    sl_level_pool pool = c.fx.pool;
+    if (c.plan.resets != SL_PLAN_RESETS_IN_KERNEL) pool.K = 0;
+    return SmallKArgs{*c.st, c.a, c.actions, c.ctp, c.ctc, c.reward, c.done, c.flags, c.ep_len,
+                      c.ep_rew, pool, c.fx.ra, c.fx.scratch};
+}
 
 __device__ __forceinline__ const SmallKArgs &kargs() {
     auto kp = __builtin_amdgcn_kernarg_segment_ptr();

@@ -705,48 +705,44 @@ bool small_shape(const sl_env_state &st) { return small_shape(st.H, st.W); }
 // boards up to 32 wide: four envs per wave (k_env_step_seg4)
 bool small_seg4_shape(int H, int W) { return small_shape(H, W) && W <= kSegW; }
 
-int launch_step_small(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
-                      const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                      uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s) {
-    if (!small_shape(st)) return SL_ETOOBIG;
-    if (st.B > 0x7FFFFFFF) return SL_EINVAL;
-    sl_level_pool pool = fx.pool;
-    if (!fx.fuse_reset || pool.H != st.H || pool.W != st.W) pool.K = 0;
-    const SmallKArgs ka{st, a, actions, ctp, ctc, reward, done, flags, ep_len, ep_rew, pool,
-                        fx.ra, fx.scratch};
+namespace {
+// replay: the actions (k_env_action, one lane per env), then each env's eligible counts
+int counts_small(const StepCall &c) {
+    const sl_env_state &st = *c.st;
+    const int rc = launch_env_action(st, c.actions, c.ctp, c.ctc,
+                                     scratch_of(c.fx.scratch, st.B).act, c.s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_stream_prologue_small, dim3((unsigned)st.B), dim3(64),
+                       (size_t)2 * st.H * 32 * sizeof(uint32_t), c.s, small_kargs(c));
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+
+template <int MODE>
+void launch_small(const sl_env_state &st, const SmallKArgs &ka, hipStream_t s) {
     const size_t lds = (size_t)3 * st.H * 32 * sizeof(uint32_t);
     const dim3 grid((unsigned)st.B);
     const bool seg = small_seg4_shape(st.H, st.W);
     const bool dppn = (st.W + 1) / 2 != 15;      // GeoSeg: DPP neighbours unless nl = 15
     const dim3 grid4((unsigned)((st.B + 3) / 4));
     const size_t lds4 = (size_t)3 * seg_stride(st.H, st.W) * sizeof(uint16_t);
-    if (fx.stream) {
-        if (stream_counts(fx)) {
-            const int rca = launch_env_action(st, actions, ctp, ctc, scratch_of(fx.scratch, st.B).act, s);
-            if (rca) return rca;
-            hipLaunchKernelGGL(k_stream_prologue_small, grid, dim3(64),
-                               (size_t)2 * st.H * 32 * sizeof(uint32_t), s, ka);
-            if (hipGetLastError() != hipSuccess) return SL_EHIP;
-        }
-        const int rc = stream_offsets(st, fx, s);
-        if (rc || !stream_steps(fx)) return rc;
-        if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
-        if (seg && dppn)
-            hipLaunchKernelGGL((k_env_step_seg4<SPAWN_STREAM, true>), grid4, dim3(64), lds4, s, ka);
-        else if (seg)
-            hipLaunchKernelGGL((k_env_step_seg4<SPAWN_STREAM, false>), grid4, dim3(64), lds4, s, ka);
-        else
-            hipLaunchKernelGGL(k_env_step_small<SPAWN_STREAM>, grid, dim3(64), lds, s, ka);
-    } else {
-        if (fx.ev_begin) (void)hipEventRecord((hipEvent_t)fx.ev_begin, s);
-        if (seg && dppn)
-            hipLaunchKernelGGL((k_env_step_seg4<SPAWN_PHILOX, true>), grid4, dim3(64), lds4, s, ka);
-        else if (seg)
-            hipLaunchKernelGGL((k_env_step_seg4<SPAWN_PHILOX, false>), grid4, dim3(64), lds4, s, ka);
-        else
-            hipLaunchKernelGGL(k_env_step_small<SPAWN_PHILOX>, grid, dim3(64), lds, s, ka);
-    }
+    if (seg && dppn)
+        hipLaunchKernelGGL((k_env_step_seg4<MODE, true>), grid4, dim3(64), lds4, s, ka);
+    else if (seg)
+        hipLaunchKernelGGL((k_env_step_seg4<MODE, false>), grid4, dim3(64), lds4, s, ka);
+    else
+        hipLaunchKernelGGL(k_env_step_small<MODE>, grid, dim3(64), lds, s, ka);
+}
+
+int step_small(const StepCall &c) {
+    if (c.plan.replay) launch_small<SPAWN_STREAM>(*c.st, small_kargs(c), c.s);
+    else launch_small<SPAWN_PHILOX>(*c.st, small_kargs(c), c.s);
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+}  // namespace
+
+const StepHooks &hooks_small() {
+    static const StepHooks h = {counts_small, nullptr, step_small, reset_scan, false};
+    return h;
 }
 
 }  // namespace sl

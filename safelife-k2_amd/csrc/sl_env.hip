@@ -13,9 +13,15 @@
 //   k_env_reset       SafeLifeEnv.reset + wrapper resets from a level pool
 //   k_env_obs         get_obs + recenter_view (safelife_env.py:125-155,
 //                     helper_utils.py:41-74)
-#include "sl_env_common.h"
+//
+// sl_env_step itself is sl_env_step.hip: plan_step decides what a step runs and
+// run_step runs it, one sequence for every kernel family.  This file holds the generic
+// family's part of it (hooks_generic(): k_env_action, k_env_count, k_env_step_generic)
+// and what every family shares after its step kernel: the follow-up reset scan
+// (reset_scan), the reset-list kernels, the observation kernels and the capture; then
+// sl_env_reset, sl_env_obs and the game-level entry points.
+#include "sl_env_step.h"
 #include "sl_env_action.h"
-#include "sl_obs.h"
 
 #include <math.h>
 
@@ -732,6 +738,9 @@ bool set_lds(const void *fn, size_t bytes) {
 
 unsigned reset_grid(int64_t B) { return (unsigned)(B < 2048 ? B : 2048); }
 
+}  // namespace
+
+namespace sl {
 bool state_ok(const sl_env_state *st) {
     return st && st->B >= 0 && st->H >= 2 && st->W >= 2 && st->board && st->goals &&
            st->start_board && (int64_t)st->H * st->W <= kMaxCells;
@@ -806,9 +815,6 @@ int launch_obs(const sl_env_state &st, const ObsArgs &a, void *out, hipStream_t 
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }
 
-}  // namespace
-
-namespace sl {
 int launch_env_action(const sl_env_state &st, const int32_t *actions, int ctp, int ctc,
                       int64_t *act, hipStream_t s) {
     hipLaunchKernelGGL(k_env_action<false>, dim3((unsigned)((st.B + 255) / 256)), dim3(256), 0,
@@ -925,9 +931,10 @@ int sl::bits_thr_check(const sl_env_state &st, const sl_mt19937 *mt, const int64
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }
 
-int sl::stream_offsets(const sl_env_state &st, const FastExtra &fx, hipStream_t s) {
+int sl::stream_offsets(const sl_env_state &st, const FastExtra &fx, bool thr_checked,
+                       hipStream_t s) {
     const Scratch sc = scratch_of(fx.scratch, st.B);
-    if (fx.mt && fx.stream_phase != 2 && !fx.thr_checked) {
+    if (fx.mt && fx.stream_phase != 2 && !thr_checked) {
         const int rcb = bits_thr_check(st, fx.mt, sc.counts, sc.err, s);
         if (rcb) return rcb;
     }
@@ -959,15 +966,14 @@ extern "C" int sl_env_reset(sl_env_state *st, const sl_level_pool *pool, const u
 static int sync_planes(const sl_env_state *st, hipStream_t s) {
     return st->planes_live ? sync_board_planes(*st, 0, s) : SL_OK;
 }
-static int demote_planes(sl_env_state *st, hipStream_t s) {
+int sl::demote_planes(sl_env_state *st, hipStream_t s) {
     if (!st->planes_live) return SL_OK;
     const int rc = sync_board_planes(*st, 1, s);
     if (!rc) st->planes_live = 0;
     return rc;
 }
 
-// replay draws from the device generator's ring (sl_env_cfg.mt) instead of cfg->draws
-static void draws_from_ring(StepArgs &a, const sl_mt19937 &mt) {
+void sl::draws_from_ring(StepArgs &a, const sl_mt19937 &mt) {
     a.draws = mt.ring;
     a.n_draws = INT64_MAX;
     a.draw_mask = mt.ring_draws - 1;
@@ -977,229 +983,59 @@ static void draws_from_ring(StepArgs &a, const sl_mt19937 &mt) {
     }
 }
 
-// Whether SL_KERNEL_AUTO takes the 33-to-64-row kernel where it exists.  Set by the A/B of
-// DESIGN.md 6.3 (profiles/mid_boards_ab.json): at 33x40, 48x48 and 64x48 it is more
-// than twice the per-cell kernel.
-constexpr bool kAutoTakesMid = true;
+// ---------------------------------------------------------------------------
+// the generic family's hooks (StepHooks, sl_env_step.h): the action of every env, one
+// lane each, with the deltas of its cell edits -- in replay before the counts, else
+// right before the step kernel
+// ---------------------------------------------------------------------------
+namespace {
+size_t generic_lds(const sl_env_state &st) { return (size_t)2 * st.H * st.W * sizeof(uint16_t); }
 
-extern "C" int sl_env_step_family(int H, int W, int kernel) {
-    if (H < 1 || W < 1) return SL_EINVAL;
-    if (kernel != SL_KERNEL_AUTO && kernel != SL_KERNEL_GENERIC && kernel != SL_KERNEL_FAST)
-        return SL_EINVAL;
-    if (kernel != SL_KERNEL_GENERIC) {
-        if (H == 64 && W == 64) return SL_FAMILY_BITS64;
-        if (H == 128 && W == 128) return SL_FAMILY_BITS128;
-        if (small_seg4_shape(H, W)) return SL_FAMILY_SMALL_SEG4;
-        if (small_shape(H, W)) return SL_FAMILY_SMALL;
-        if (mid_shape(H, W) && (kAutoTakesMid || kernel == SL_KERNEL_FAST)) return SL_FAMILY_MID;
-    }
-    return kernel == SL_KERNEL_FAST ? SL_ETOOBIG : SL_FAMILY_GENERIC;
+int generic_action(const StepCall &c) {
+    const sl_env_state &st = *c.st;
+    hipLaunchKernelGGL(k_env_action<true>, dim3((unsigned)((st.B + 255) / 256)), dim3(256), 0,
+                       c.s, st, c.actions, c.ctp, c.ctc, scratch_of(c.fx.scratch, st.B).act);
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }
 
-extern "C" int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const int32_t *actions,
-                           const sl_env_cfg *cfg, double *reward, uint8_t *done,
-                           uint8_t *info_flags, int32_t *ep_len, int32_t *ep_reward,
-                           void *stream) {
-    if (!state_ok(st) || !cfg || !actions || !reward || !done || !cfg->scratch) return SL_EINVAL;
-    if (cfg->bonus_period < 0 || cfg->bonus_period > SL_BONUS_PERIOD_MAX) return SL_EINVAL;
-    if (cfg->bonus_period > 0 && (!cfg->bonus_table || cfg->bonus_len < 1)) return SL_EINVAL;
-    if (cfg->auto_reset && (!pool || !info_flags || pool->K <= 0 || pool->H != st->H ||
-                            pool->W != st->W))
-        return SL_EINVAL;
-    const int64_t B = st->B;
-    if (B == 0) return SL_OK;
-    hipStream_t s = (hipStream_t)stream;
-    Scratch sc = scratch_of(cfg->scratch, B);
-    const size_t lds = (size_t)2 * st->H * st->W * sizeof(uint16_t);
+int generic_counts(const StepCall &c) {
+    const sl_env_state &st = *c.st;
+    const int rc = generic_action(c);
+    if (rc) return rc;
+    if (!set_lds((const void *)k_env_count, generic_lds(st))) return SL_ETOOBIG;
+    hipLaunchKernelGGL(k_env_count, dim3((unsigned)st.B), dim3(NT), generic_lds(st), c.s, st,
+                       scratch_of(c.fx.scratch, st.B).counts);
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
 
-    StepArgs a;
-    a.time_limit = cfg->time_limit;
-    a.auto_reset = cfg->auto_reset;
-    a.bonus_len = cfg->bonus_len;
-    a.bonus_period = cfg->bonus_period;
-    a.penalty_coef = cfg->penalty_coef;
-    a.bonus_table = cfg->bonus_table;
-    a.seed = cfg->seed;
-    a.step = cfg->step;
-    a.env0 = cfg->env0;
-    a.draws = cfg->draws;
-    a.n_draws = cfg->n_draws;
+int generic_pre_step(const StepCall &c) { return c.plan.replay ? SL_OK : generic_action(c); }
 
-    if (cfg->rng_mode != SL_RNG_STREAM && cfg->rng_mode != SL_RNG_PHILOX) return SL_EINVAL;
-    const bool replay = cfg->rng_mode == SL_RNG_STREAM;
-    if (replay && cfg->mt) draws_from_ring(a, *cfg->mt);
-    if (replay && (!cfg->stream_pos || (!a.draws && a.n_draws > 0))) return SL_EINVAL;
-    if (cfg->stream_phase < 0 || cfg->stream_phase > 2 || (cfg->stream_phase && !replay) ||
-        (cfg->stream_phase == 2 && !cfg->stream_base))
-        return SL_EINVAL;
-    // the kernel family is sl_env_step_family's answer (SL_KERNEL_BANDS names a
-    // side-effect rollout kernel, no step kernel: SL_EINVAL); `small` stands for every
-    // one-wave kernel with the uint16 board in HBM that resets its own finished envs
-    const int family = sl_env_step_family(st->H, st->W, cfg->kernel);
-    if (family < 0) return family;
-    const bool fast = family == SL_FAMILY_BITS64;
-    // (the 128x128 kernel needs the state's goals mirror as well)
-    const bool fast128 = family == SL_FAMILY_BITS128 && bits128_shape(*st);
-    if (family == SL_FAMILY_BITS128 && !fast128 && cfg->kernel == SL_KERNEL_FAST) return SL_ETOOBIG;
-    const bool mid = family == SL_FAMILY_MID;
-    const bool small = mid || family == SL_FAMILY_SMALL || family == SL_FAMILY_SMALL_SEG4;
-    bool reset_done = false;
-    FastExtra fx;
-    fx.fuse_reset = cfg->auto_reset ? 1 : 0;
-    if (pool) fx.pool = *pool;
-    else fx.pool = sl_level_pool{};
-    fx.ra = reset_args(cfg);
-    fx.scratch = cfg->scratch;
-    fx.ev_end = cfg->ev_end;
-    const sl_capture *cap = (cfg->capture && cfg->capture->n > 0) ? cfg->capture : nullptr;
-    // (env and flags are needed; every other target may be NULL and is then not copied)
-    if (cap && (!cap->env || !cap->flags || !info_flags || !cfg->auto_reset)) return SL_EINVAL;
-    fx.capture = cap;
-    fx.stream = replay ? 1 : 0;
-    fx.stream_pos = cfg->stream_pos;
-    fx.stream_phase = cfg->stream_phase;
-    fx.stream_base = cfg->stream_base;
-    fx.mt = replay ? cfg->mt : nullptr;
-    if (fx.mt && fx.mt->bit_ring) fx.bits_thr = fx.mt->bits_thr;
-    fx.ev_begin = cfg->ev_begin;
-    // the small-board kernel resets finished envs inside the step; with a capture the
-    // resets run in the follow-up scan so the pre-reset frame can be copied first.
-    // The 64x64 / 128x128 launchers copy that frame between their step kernel and
-    // their reset-list kernel, so they keep the list (and its per-parity lengths,
-    // which only the reset-list kernel clears) going through captured steps.
-    if (cap && small) fx.fuse_reset = 0;
-    ObsArgs oa;
-    if (cfg->obs_out) {
-        const int rc = obs_args(cfg->obs_vh, cfg->obs_vw, cfg->obs_remove_white, cfg->obs_mode,
-                                cfg->obs_channels, cfg->obs_nch, &oa);
-        if (rc) return rc;
-    }
-    // 128x128 board planes: a step of the fast kernel without capture keeps the board
-    // in them -- with no views, or with packed views of at most kViewMaxRows rows,
-    // which the step kernel writes from the planes (fuse_obs128); any other step first
-    // completes (and demotes) it.  (Replay: with draw planes, the decided form.)
-    const bool planes128 = st->board_planes && st->planes_ok && st->H == 128 && st->W == 128;
-    if (cfg->board_mode != SL_BOARD_AUTO && cfg->board_mode != SL_BOARD_UINT16) return SL_EINVAL;
-    if (cfg->planes64_waves != 0 && cfg->planes64_waves != 5 && cfg->planes64_waves != 6 &&
-        cfg->planes64_waves != SL_PLANES64_W6_UNSPLIT)
-        return SL_EINVAL;
-    const bool fuse_obs128 = fast128 && planes128 && cfg->obs_out && !cap &&
-                             cfg->board_mode != SL_BOARD_UINT16 &&
-                             (!replay || st->elig_planes) && oa.mode == SL_OBS_PACKED &&
-                             oa.vh <= kViewMaxRows128 && oa.vw <= 128;
-    fx.plane_mode = (fast128 && planes128 && (!cfg->obs_out || fuse_obs128) && !cap &&
-                     (!replay || st->elig_planes) && cfg->board_mode != SL_BOARD_UINT16) ? 1 : 0;
-    // observations: packed views of 64x64 boards come out of the step kernel itself
-    // ... and channel views too (one wave writes its env's 16-byte chunks from the
-    // view masks it builds in LDS: views up to kFusedChanCells cells, 16-B aligned out)
-    const bool fuse_obs =
-        cfg->obs_out && fast &&
-        ((oa.mode == SL_OBS_PACKED && oa.vh * oa.vw <= kObsMaxCells) ||
-         (oa.mode != SL_OBS_PACKED && oa.vh <= 64 && oa.vw <= 64 &&
-          oa.vh * oa.vw + 2 <= kFusedChanCells && (((uintptr_t)cfg->obs_out) & 15) == 0));
-    // 64x64: a Philox step without capture and with no views, or with views the step
-    // kernel writes itself (fuse_obs: from the planes, sl_bits.hip, plane mode)
-    const bool planes64 = planes64_shape(*st);
-    if (planes64)
-        fx.plane_mode = (fast && !cap && !replay && cfg->board_mode != SL_BOARD_UINT16 &&
-                         (!cfg->obs_out || fuse_obs)) ? 1 : 0;
-    if ((planes128 || planes64) && !fx.plane_mode) {
-        const int rc = demote_planes(st, s);
-        if (rc) return rc;
-    }
-    // (a plane-mode step below leaves boards in planes)
-    if (fx.plane_mode && cfg->stream_phase != 1) st->planes_live = 1;
-    fx.obs_out = (fuse_obs || fuse_obs128) ? (uint16_t *)cfg->obs_out : nullptr;
-    fx.obs_vh = cfg->obs_vh;
-    fx.obs_vw = cfg->obs_vw;
-    fx.obs_rw = cfg->obs_remove_white;
-    fx.obs_mode = SL_OBS_PACKED;
-    fx.obs_nch = 0;
-    fx.obs_chpack = 0;
-    fx.obs_one = 1u;
-    if (cfg->obs_out) {
-        fx.obs_mode = oa.mode;
-        fx.obs_nch = oa.nch;
-        for (int k = 0; k < oa.nch; k++) fx.obs_chpack |= (uint64_t)oa.ch[k] << (4 * k);
-        fx.obs_one = oa.mode == SL_OBS_CHANNELS_F32 ? 0x3F800000u
-                     : oa.mode == SL_OBS_CHANNELS_BF16 ? 0x3F80u : 1u;
-    }
-    if (fast128) {
-        int rc = launch_step_bits128(*st, a, fx, actions, cfg->can_toggle_powers,
-                                     cfg->can_toggle_colors, reward, done, info_flags, ep_len,
-                                     ep_reward, s);
-        if (rc || cfg->stream_phase == 1) return rc;
-        reset_done = fx.fuse_reset && fx.pool.K > 0;
-    } else if (small) {
-        int rc = (mid ? launch_step_mid : launch_step_small)(
-            *st, a, fx, actions, cfg->can_toggle_powers, cfg->can_toggle_colors, reward, done,
-            info_flags, ep_len, ep_reward, s);
-        if (rc || cfg->stream_phase == 1) return rc;
-        reset_done = fx.fuse_reset && fx.pool.K > 0 && fx.pool.H == st->H && fx.pool.W == st->W;
-    } else if (fast) {
-        int rc = launch_step_bits(*st, a, fx, actions, cfg->can_toggle_powers,
-                                  cfg->can_toggle_colors, reward, done, info_flags, ep_len,
-                                  ep_reward, s, cfg->planes64_waves);
-        if (rc || cfg->stream_phase == 1) return rc;
-        reset_done = fx.fuse_reset && fx.pool.K > 0;
-    } else {
-        if (!replay || stream_counts(fx)) {
-            hipLaunchKernelGGL(k_env_action<true>, dim3((unsigned)((B + 255) / 256)), dim3(256), 0,
-                               s, *st, actions, cfg->can_toggle_powers, cfg->can_toggle_colors,
-                               sc.act);
-            if (hipGetLastError() != hipSuccess) return SL_EHIP;
-        }
-        if (replay) {
-            if (stream_counts(fx)) {
-                if (!set_lds((const void *)k_env_count, lds)) return SL_ETOOBIG;
-                hipLaunchKernelGGL(k_env_count, dim3((unsigned)B), dim3(NT), lds, s, *st, sc.counts);
-                if (hipGetLastError() != hipSuccess) return SL_EHIP;
-            }
-            int rc = stream_offsets(*st, fx, s);
-            if (rc || cfg->stream_phase == 1) return rc;
-            if (!set_lds((const void *)k_env_step_generic<SL_RNG_STREAM>, lds)) return SL_ETOOBIG;
-            hipLaunchKernelGGL(k_env_step_generic<SL_RNG_STREAM>, dim3((unsigned)B), dim3(NT), lds,
-                               s, *st, a, sc.act, sc.offsets, sc.err, reward, done, info_flags,
-                               ep_len, ep_reward);
-        } else {
-            if (!set_lds((const void *)k_env_step_generic<SL_RNG_PHILOX>, lds)) return SL_ETOOBIG;
-            if (cfg->ev_begin) (void)hipEventRecord((hipEvent_t)cfg->ev_begin, s);
-            hipLaunchKernelGGL(k_env_step_generic<SL_RNG_PHILOX>, dim3((unsigned)B), dim3(NT), lds,
-                               s, *st, a, sc.act, sc.offsets, sc.err, reward, done, info_flags,
-                               ep_len, ep_reward);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) return SL_EHIP;
-    // the bit-sliced 64x64 / 128x128 launchers record ev_end themselves, between the
-    // step kernel and their reset-list kernel
-    if (cfg->ev_end && !fast && !fast128) (void)hipEventRecord((hipEvent_t)cfg->ev_end, s);
+template <int RNG>
+int generic_step_k(const StepCall &c) {
+    const sl_env_state &st = *c.st;
+    const Scratch sc = scratch_of(c.fx.scratch, st.B);
+    if (!set_lds((const void *)k_env_step_generic<RNG>, generic_lds(st))) return SL_ETOOBIG;
+    hipLaunchKernelGGL(k_env_step_generic<RNG>, dim3((unsigned)st.B), dim3(NT), generic_lds(st),
+                       c.s, st, c.a, sc.act, sc.offsets, sc.err, c.reward, c.done, c.flags,
+                       c.ep_len, c.ep_rew);
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
 
-    if (cap && !fast && !fast128) {
-        const int rc = launch_capture(*st, *cap, info_flags, 0, s);
-        if (rc) return rc;
-    }
-    if (cfg->auto_reset && !reset_done) {
-        hipLaunchKernelGGL(k_env_reset_scan, dim3((unsigned)((B + NT - 1) / NT)), dim3(NT), 0, s,
-                           *st, *pool, (const uint8_t *)info_flags, reset_args(cfg));
-        if (hipGetLastError() != hipSuccess) return SL_EHIP;
-    }
-    if (cfg->obs_out) {
-        if (fuse_obs128) {
-            // the step kernel wrote every view from the planes; the envs the reset-list
-            // kernel reset get theirs from the new episode's uint16 board
-            if (reset_done) {
-                const int rc = launch_obs_reset_list(*st, oa, (uint16_t *)cfg->obs_out,
-                                                     cfg->scratch, cfg->step, s);
-                if (rc) return rc;
-            }
-        } else if (!fuse_obs || (cfg->auto_reset && !reset_done)) {
-            const int rc = launch_obs(*st, oa, cfg->obs_out, s);
-            if (rc) return rc;
-        }
-        // else: the reset-list kernel wrote the views of the envs it reset
-    }
-    if (cap) return launch_capture(*st, *cap, info_flags, 1, s);
-    return SL_OK;
+int generic_step(const StepCall &c) {
+    return c.plan.replay ? generic_step_k<SL_RNG_STREAM>(c) : generic_step_k<SL_RNG_PHILOX>(c);
+}
+}  // namespace
+
+int sl::reset_scan(const StepCall &c) {
+    const sl_env_state &st = *c.st;
+    hipLaunchKernelGGL(k_env_reset_scan, dim3((unsigned)((st.B + NT - 1) / NT)), dim3(NT), 0, c.s,
+                       st, c.fx.pool, (const uint8_t *)c.flags, c.fx.ra);
+    return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+}
+
+const StepHooks &sl::hooks_generic() {
+    static const StepHooks h = {generic_counts, generic_pre_step, generic_step, reset_scan, false};
+    return h;
 }
 
 // ---------------------------------------------------------------------------

@@ -349,20 +349,16 @@ struct FastExtra {
     const sl_mt19937 *mt;   // replay from the device generator (sl_env_cfg.mt) or NULL:
                             // stream_offsets fills its ring for the step's range
     double bits_thr = -1.0; // the device generator's bit ring: its threshold (else < 0);
-    int32_t thr_checked = 0;// the 128x128 count prologue checks it (stream_offsets then
-                            // launches no k_bits_thr_check)
+    int32_t thr_checked = 0;// (unused: the kernel arguments keep their layout)
     int32_t plane_mode = 0; // 128x128 step without capture (no views, or packed views of
                             // <= kViewMaxRows128 rows written from the planes; replay
                             // with draw planes), board_planes set: the board is kept in
                             // sl_env_state.board_planes
 };
-// replay-mode phases of a bit-sliced launcher: whether it runs the action + count
-// prologue, and whether it continues past the offsets scan to the step kernel
-__host__ inline bool stream_counts(const FastExtra &fx) { return fx.stream_phase != 2; }
-__host__ inline bool stream_steps(const FastExtra &fx) { return fx.stream_phase != 1; }
 // replay mode: exclusive scan of the prologue's per-(env, tensor) eligible counts into
-// each tensor's first uniform, advancing *fx.stream_pos (sl_env.hip)
-int stream_offsets(const sl_env_state &st, const FastExtra &fx, hipStream_t s);
+// each tensor's first uniform, advancing *fx.stream_pos (sl_env.hip).  thr_checked: the
+// count prologue has checked the bit ring's threshold (else bits_thr_check runs here)
+int stream_offsets(const sl_env_state &st, const FastExtra &fx, bool thr_checked, hipStream_t s);
 // the device generator's bit ring: flag (err |= 1) any env with draws this step whose
 // threshold is not the ring's (sl_env.hip)
 int bits_thr_check(const sl_env_state &st, const sl_mt19937 *mt, const int64_t *counts,
@@ -372,8 +368,7 @@ int bits_thr_check(const sl_env_state &st, const sl_mt19937 *mt, const int64_t *
 int launch_capture(const sl_env_state &st, const sl_capture &c, const uint8_t *flags, int phase,
                    hipStream_t s);
 // bit-sliced 128x128 kernel (sl_bits128.hip); needs the goals mirror (st.planes).
-// With fx.fuse_reset it queues the envs that finished and launches
-// k_env_reset_list_wide for them.
+// With fx.fuse_reset it queues the envs that finished for k_env_reset_list_wide.
 bool bits128_shape(const sl_env_state &st);
 // the bit-sliced kernel for boards up to 32 x 64 (sl_bits_small.hip)
 bool small_shape(const sl_env_state &st);
@@ -381,18 +376,9 @@ bool small_shape(int H, int W);
 // ... of which the shapes that run four envs per wave
 bool small_seg4_shape(int H, int W);
 // the bit-sliced kernel for boards of 33 to 64 rows and up to 64 columns, 64x64 aside
-// (sl_bits_mid.hip); resets as launch_step_small
+// (sl_bits_mid.hip); auto-reset in both: envs whose episode ended are reset by their
+// own wave from the pool
 bool mid_shape(int H, int W);
-int launch_step_mid(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
-                    const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                    uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s);
-// (auto-reset: envs whose episode ended are reset by their own wave from fx.pool)
-int launch_step_small(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
-                      const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                      uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s);
-int launch_step_bits128(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
-                        const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                        uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s);
 // the action of every env (k_env_action, one lane per env): state and cell edits in
 // HBM, reward into act[b]; the 128x128 kernel's pre-pass (sl_env.hip)
 // 128x128 board planes (sl_env_state.board_planes): complete the uint16 board of envs
@@ -412,10 +398,5 @@ int launch_reset_list_wide(const sl_env_state &st, const sl_level_pool &pool, co
 // the 128x128 step kernel writes packed views of at most this many rows from the board
 // planes (sl_bits128.hip view_band: one run of view rows per 32-row band)
 constexpr int kViewMaxRows128 = 96;
-// bit-sliced 64x64 kernel (sl_bits.hip)
-int launch_step_bits(const sl_env_state &st, const StepArgs &a, const FastExtra &fx,
-                     const int32_t *actions, int ctp, int ctc, double *reward, uint8_t *done,
-                     uint8_t *flags, int32_t *ep_len, int32_t *ep_rew, hipStream_t s,
-                     int planes64_waves = 0);   // sl_env_cfg.planes64_waves
 
 }  // namespace sl

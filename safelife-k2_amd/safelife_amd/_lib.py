@@ -23,6 +23,13 @@ SL_KERNEL_MID = 4       # sl_side_effect_densities_k only: the one-wave rollout 
 FAMILY_NAMES = {SL_FAMILY_GENERIC: "generic", SL_FAMILY_SMALL_SEG4: "small-seg4",
                 SL_FAMILY_SMALL: "small", SL_FAMILY_MID: "mid", SL_FAMILY_BITS64: "bits64",
                 SL_FAMILY_BITS128: "bits128"}
+# sl_step_plan (sl_env_step_plan): who writes the views, who resets, the 64x64 instance
+SL_PLAN_OBS_NONE, SL_PLAN_OBS_FUSED64, SL_PLAN_OBS_FUSED128, SL_PLAN_OBS_SEPARATE = range(4)
+(SL_PLAN_RESETS_NONE, SL_PLAN_RESETS_IN_KERNEL, SL_PLAN_RESETS_LIST64,
+ SL_PLAN_RESETS_SPLIT_TAIL64, SL_PLAN_RESETS_LIST128, SL_PLAN_RESETS_SCAN) = range(6)
+(SL_PLAN_K64_NONE, SL_PLAN_K64_BITS64, SL_PLAN_K64_PLANES, SL_PLAN_K64_GRAY, SL_PLAN_K64_W6,
+ SL_PLAN_K64_S6, SL_PLAN_K64_CHAN) = range(7)
+SL_PLAN_KEEP_RUNTIME, SL_PLAN_KEEP_C3, SL_PLAN_KEEP_ALL = range(3)
 SL_STREAM_ERR_RANGE, SL_STREAM_ERR_THRESHOLD = 1, 2
 # sl_emd_cells_device: the size limit of a problem and the negative status codes
 SL_EMD_DEVICE_MAX_CELLS = 256
@@ -88,6 +95,13 @@ class EnvCfg(ctypes.Structure):
                 ("board_mode", i32), ("planes64_waves", i32)]
 
 
+class StepPlan(ctypes.Structure):
+    """sl_step_plan: what sl_env_step would run (sl_env_step_plan; host only)."""
+    _fields_ = [(n, i32) for n in ("empty", "family", "replay", "stream_phase", "plane_mode",
+                                   "demote_first", "obs", "resets", "capture", "kernel64",
+                                   "keep", "view_kind")]
+
+
 class MT19937(ctypes.Structure):
     _fields_ = [("n_chains", i32), ("rounds", i32), ("ring_draws", i64), ("ring", vp),
                 ("chains", vp), ("prefix", vp), ("polys", vp), ("ctl", vp),
@@ -144,6 +158,10 @@ def lib():
     if hasattr(L, "sl_env_step_family") or LIB_PATH == _DEFAULT_LIB:
         L.sl_env_step_family.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.sl_env_step_family.restype = ctypes.c_int
+    if hasattr(L, "sl_env_step_plan") or LIB_PATH == _DEFAULT_LIB:
+        L.sl_env_step_plan.argtypes = [ctypes.POINTER(EnvState), ctypes.POINTER(LevelPool),
+                                       ctypes.POINTER(EnvCfg), vp, ctypes.POINTER(StepPlan)]
+        L.sl_env_step_plan.restype = ctypes.c_int
     L.sl_env_reset.argtypes = [ctypes.POINTER(EnvState), ctypes.POINTER(LevelPool), vp,
                                ctypes.POINTER(EnvCfg), vp]
     L.sl_level_pool_prepare.argtypes = [ctypes.POINTER(LevelPool), vp]

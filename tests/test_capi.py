@@ -57,7 +57,8 @@ def test_struct_layout_matches_header(tmp_path):
     """Compile a tiny C program with the header and compare offsets with ctypes."""
     from safelife_amd import _lib
     fields = {"sl_env_state": _lib.EnvState, "sl_level_pool": _lib.LevelPool,
-              "sl_env_cfg": _lib.EnvCfg, "sl_capture": _lib.Capture, "sl_mt19937": _lib.MT19937}
+              "sl_env_cfg": _lib.EnvCfg, "sl_capture": _lib.Capture, "sl_mt19937": _lib.MT19937,
+              "sl_step_plan": _lib.StepPlan}
     lines = []
     for cname, cls in fields.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
