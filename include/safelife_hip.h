@@ -588,6 +588,32 @@ typedef struct sl_env_state {
                                  planes_ok change; never set again while envs run
                                  whose goals are not known.  0 = goals of any
                                  colour.  128x128 kernels ignore it.             */
+    uint32_t derived_planes;  /* 64x64 plane mode: cell bits (planes), of 8 and 15
+                                 (mask 0x8100), that every board of the batch holds
+                                 but that follow from the rest of the env's state,
+                                 for good (the caller's promise, for its levels and
+                                 written boards):
+                                 bit 15: plane 15 equals plane 2 in every cell (only
+                                 a crate carries either bit; actions move whole cells
+                                 or write LIFE | colour, the rule clears both
+                                 together; needs can_toggle_powers == 0, or the agent
+                                 can take bit 2 alone);
+                                 bit 8: the cells with EXIT are exactly the env's
+                                 exit list (exit_y, exit_x, exit_count <=
+                                 SL_MAX_EXITS; an exit is frozen, never pushed,
+                                 made or destroyed).
+                                 Their planes are neither loaded nor stored: the
+                                 kernels rebuild them in registers, and
+                                 sl_env_board_sync puts them into the completed
+                                 uint16 board.  The stored words are packed
+                                 without them, so the flag changes the layout: it
+                                 changes as agent_planes does (complete the board
+                                 first and clear SL_POK_BOARD; clearing bits is
+                                 always safe then).  The kernels derive both
+                                 planes or neither: one bit alone counts as none.
+                                 Bits outside 0x8100, in board_zero or in
+                                 agent_planes are ignored.  0 = none.  128x128
+                                 kernels ignore it.                              */
 } sl_env_state;
 
 /*
@@ -861,6 +887,11 @@ typedef struct sl_step_plan {
     int32_t keep;           /* SL_PLAN_KEEP_* (kernel64 PLANES, GRAY, W6, S6, CHAN)       */
     int32_t view_kind;      /* views the step kernel writes: 0 none, 1 packed, 2 u16 / bf16
                                channels, 3 u8 channels, 4 f32 channels                    */
+    int32_t stored;         /* 64x64 plane mode: the board planes the step loads and stores
+                               (held, not the agent's, not derived); 0x061D for the C3 / C4
+                               planes with agent planes 0x0062 and derived planes 0x8100   */
+    int32_t derived;        /* 64x64 plane mode: the planes of sl_env_state.derived_planes
+                               the step rebuilds in registers (0x8100 less board_zero, or 0) */
 } sl_step_plan;
 
 /* Same return codes as sl_env_step for anything it rejects before launching

@@ -863,8 +863,9 @@ k_env_step_bits64(StepKArgs ka) {
 // sl_env_state.board_zero (all zero in every board of the batch, for good: the C3 / C4
 // pools never use cell bits 7 and 11-14) are neither loaded nor stored, nor are the
 // planes in sl_env_state.agent_planes (one cell each, the agent's: built from its
-// position), and the stored ones are packed (PlaneSlots): on C3 / C4 4 of the 8 KiB are
-// read.  SL_POK_BOARD_PLANES: the
+// position) or in sl_env_state.derived_planes (plane 15, a copy of plane 2; plane 8, the
+// env's exit list), and the stored ones are packed (PlaneSlots): on C3 / C4 3 of the 8 KiB
+// are read.  SL_POK_BOARD_PLANES: the
 // planes hold the board; SL_POK_BOARD_FULL: so does the uint16 board (a sync wrote it),
 // which a plane step otherwise leaves stale (exits aside: the epilogue writes them in
 // both).
@@ -882,37 +883,78 @@ k_env_step_bits64(StepKArgs ka) {
 // the instantiations: every plane, the C3 / C4 pools' planes (cell bits 0-6, 8-10, 15,
 // of which the agent's 1, 5, 6 are implied), and any other masks at run time
 constexpr u32 kKeepAll = 0xFFFFu, kKeepC3 = 0x877Fu, kAgentC3 = 0x0062u;
-template <u32 K16>       // the held planes, fixed at compile time; 0: from board_zero
+// Derived planes (sl_env_state.derived_planes): planes a board holds that are neither
+// loaded nor stored but rebuilt in registers once the stored words are read -- plane 15, a
+// copy of plane 2 (only the crate carries either bit; taken after mux_edits, so the action's
+// edits reach both), and plane 8, one bit per exit of the record's exit list (at most
+// SL_MAX_EXITS, built as agent_words builds the agent's).  The stored words are packed
+// without them: C3 / C4 12 words, three DMA groups, instead of 16 and four.  As with the
+// other two masks the layout changes only after every board has left the planes.
+constexpr u32 kDerivable = 0x8100u;
+// the derived planes a state's flag stands for: both, or none (a batch with half the
+// property stores both planes)
+__host__ __device__ constexpr u32 derived_eff(u32 derived) {
+    return (derived & kDerivable) == kDerivable ? kDerivable : 0u;
+}
+// K16: the held planes, fixed at compile time; 0: from board_zero.  DM: the derived planes,
+// fixed at compile time (the kKeepC3 instances: 0x8100, and 0 in their k_env_p64_stored16
+// twins; every position a constant in both); -1: from derived_planes
+template <u32 K16, int DM = -1>
 struct PlaneSlots {
     // kKeepC3 fixes the agent planes too (the dispatch checks both); the other two
     // take them at run time
     static constexpr bool kFixed = K16 == kKeepC3;
     u32 keep;           // bit q: word q is held (K16 == 0)
-    u32 store;          // bit q: word q is stored (!kFixed)
+    u32 store;          // bit q: word q has a position in the layout (!kFixed)
+    u32 drv_;           // bit p: plane p (of kDerivable, in the layout) is derived (DM < 0)
+    __device__ __forceinline__ u32 drv16() const { return DM >= 0 ? (u32)DM : drv_; }
     __device__ __forceinline__ u32 keep32() const { return K16 ? K16 * 0x10001u : keep; }
     __device__ __forceinline__ u32 store32() const {
         return kFixed ? (K16 & ~kAgentC3) * 0x10001u : store;
     }
+    static constexpr bool late(int q) { return (kDerivable >> (q & 15)) & 1u; }
     __device__ __forceinline__ bool kept(int q) const { return (keep32() >> q) & 1u; }
-    __device__ __forceinline__ bool stored(int q) const { return (store32() >> q) & 1u; }
-    // the agent planes (held, not stored)
+    __device__ __forceinline__ bool laid(int q) const { return (store32() >> q) & 1u; }
+    // loaded and stored: held, not the agent's and not derived
+    __device__ __forceinline__ bool stored(int q) const {
+        return laid(q) && !(late(q) && ((drv16() >> (q & 15)) & 1u));
+    }
+    __device__ __forceinline__ u32 stored32() const { return store32() & ~(drv16() * 0x10001u); }
+    // the agent planes (held, not stored or derived)
     __device__ __forceinline__ u32 agent16() const {
         return kFixed ? kAgentC3 : (keep32() & ~store32()) & 0xFFFFu;
     }
     // (at run time recomputed where used: two SALU, not 32 positions held in SGPRs all
-    // kernel long; with kFixed a constant)
+    // kernel long; with kFixed and DM a constant)
     __device__ __forceinline__ int pos(int q) const {
-        if (kFixed) return __builtin_popcount(store32() & ((1u << q) - 1u));
-        u32 k = store;
+        const u32 below = (1u << q) - 1u;
+        if (kFixed && DM >= 0) return __builtin_popcount(stored32() & below);
+        u32 k = stored32();
         asm volatile("" : "+s"(k));
-        return __builtin_popcount(k & ((1u << q) - 1u));
+        return __builtin_popcount(k & below);
     }
-    __device__ __forceinline__ int stored16() const { return __builtin_popcount(store32() & 0xFFFFu); }
-    static __device__ __forceinline__ PlaneSlots of(u32 zero, u32 agent) {
+    __device__ __forceinline__ int stored16() const {
+        return __builtin_popcount(stored32() & 0xFFFFu);
+    }
+    static __device__ __forceinline__ PlaneSlots of(u32 zero, u32 agent, u32 derived) {
         const u32 k = ~zero & 0xFFFFu;
-        return PlaneSlots{k * 0x10001u, (k & ~agent) * 0x10001u};
+        const u32 s = kFixed ? (K16 & ~kAgentC3) : ((K16 ? K16 : k) & ~agent);
+        return PlaneSlots{k * 0x10001u, (k & ~agent) * 0x10001u, derived_eff(derived) & s};
     }
 };
+// this lane's two words of the exit plane: one bit per exit of the record's list
+__device__ __forceinline__ void exit_words(u32 V, int lane, u32 ew[2]) {
+    const RecFields fl{V, 0, 0, 0, 0.0};
+    const int n = min(fl.exit_count(), SL_MAX_EXITS);
+    ew[0] = ew[1] = 0u;
+#pragma unroll 1
+    for (int e = 0; e < n; e++) {
+        const int y = fl.exit_y(e), x = fl.exit_x(e);
+        const u32 bit = lane == 2 * (x >> 1) + (y >> 5) ? 1u << (y & 31) : 0u;
+        if (x & 1) ew[1] |= bit;
+        else ew[0] |= bit;
+    }
+}
 // this lane's two words of an agent plane: the one bit of cell (ay, ax)
 __device__ __forceinline__ void agent_words(int ay, int ax, int lane, u32 aw[2]) {
     const u32 bit = lane == 2 * (ax >> 1) + (ay >> 5) ? 1u << (ay & 31) : 0u;
@@ -930,8 +972,8 @@ constexpr int planes_min_waves(u32 k16, int obs) {
 
 // the stored plane words of an env, DMA'd into the wave's buffer in their packed order
 // (position p of lane l at buf[p * 64 + l]); no registers held while they are in flight
-template <u32 K16>
-__device__ __forceinline__ void dma_planes(const u32 *__restrict__ bp, PlaneSlots<K16> ps,
+template <u32 K16, int DM>
+__device__ __forceinline__ void dma_planes(const u32 *__restrict__ bp, PlaneSlots<K16, DM> ps,
                                            lds_u32 *buf, int lane) {
     const int groups = (2 * ps.stored16() + 3) >> 2;
     const char *s = reinterpret_cast<const char *>(bp);
@@ -962,10 +1004,13 @@ struct NearCells {
         return (u32)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane(k));
     }
 };
-// cell i from the staged planes (this lane's; planes not stored are 0: the caller adds
-// the agent planes to the agent's cell)
-template <u32 K16>
-__device__ __forceinline__ u32 lds_plane_cell(const lds_u32 *buf, PlaneSlots<K16> ps, int i) {
+// cell i from the staged planes (this lane's; of the planes not stored, the derived ones
+// are rebuilt from plane 2 and the record's exit list -- the action tests EXIT on these
+// cells and moves crates whole -- and the agent planes are 0: the caller adds them to the
+// agent's cell)
+template <u32 K16, int DM>
+__device__ __forceinline__ u32 lds_plane_cell(const lds_u32 *buf, PlaneSlots<K16, DM> ps, u32 V,
+                                              int i) {
     const int y = i >> 6, x = i & 63;
     const lds_u32 *q = buf + 2 * (x >> 1) + (y >> 5);
     const u32 r = (u32)(y & 31);
@@ -976,10 +1021,21 @@ __device__ __forceinline__ u32 lds_plane_cell(const lds_u32 *buf, PlaneSlots<K16
         const int pw = ps.pos(p) + (w ? ps.stored16() : 0);
         if (ps.stored(p)) v |= ((q[pw * 64] >> r) & 1u) << p;
     }
+    if (ps.drv16() & 0x8000u) v |= (v & 4u) << 13;
+    if (ps.drv16() & 0x0100u) {
+        const RecFields fl{V, 0, 0, 0, 0.0};
+        const int n = min(fl.exit_count(), SL_MAX_EXITS);
+#pragma unroll 1
+        for (int e = 0; e < n; e++)
+            if (i == fl.exit_y(e) * 64 + fl.exit_x(e)) v |= 0x0100u;
+    }
     return v;
 }
 
-// The step itself is sl_planes64_step.inc, shared with k_env_planes64_chan below.
+// The step itself is sl_planes64_step.inc, shared with k_env_planes64_chan below.  The
+// kKeepC3 instances have the derived planes compiled in as well (DM 0x8100: twelve stored
+// words, every position a constant); a C3 batch without them runs k_env_p64_stored16.
+constexpr int planes_dm(u32 k16) { return k16 == kKeepC3 ? (int)kDerivable : -1; }
 // OBS: 0 no views, 1 packed views
 template <u32 K16, int OBS>
 __global__ void __launch_bounds__(64, planes_min_waves(K16, OBS))
@@ -987,6 +1043,7 @@ k_env_step_bits64_planes(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     uint16_t *const vm = nullptr;
     constexpr bool GRAY = false, W6 = false, SPLIT_EPI = false;
+    constexpr int DM = planes_dm(K16);
 #include "sl_planes64_step.inc"
 }
 
@@ -1003,6 +1060,7 @@ k_env_planes64_gray(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) u32 stage[N * N / 2];
     uint16_t *const vm = nullptr;
     constexpr bool GRAY = true, W6 = false, SPLIT_EPI = false;
+    constexpr int DM = planes_dm(K16);
 #include "sl_planes64_step.inc"
 }
 
@@ -1023,6 +1081,7 @@ k_env_planes64_w6(StepKArgs ka) {
     uint16_t *const vm = nullptr;
     constexpr int OBS = 0;
     constexpr bool GRAY = true, W6 = true, SPLIT_EPI = false;
+    constexpr int DM = planes_dm(K16);
 #include "sl_planes64_step.inc"
 }
 
@@ -1039,6 +1098,7 @@ k_env_planes64_s6(StepKArgs ka) {
     uint16_t *const vm = nullptr;
     constexpr int OBS = 0;
     constexpr bool GRAY = true, W6 = true, SPLIT_EPI = true;
+    constexpr int DM = planes_dm(K16);
 #include "sl_planes64_step.inc"
 }
 
@@ -1104,6 +1164,28 @@ k_env_planes64_chan(StepKArgs ka) {
     __shared__ __attribute__((aligned(16))) uint16_t vmask[sl::obs::kFusedChanCells];
     uint16_t *const vm = vmask;
     constexpr bool GRAY = false, W6 = false, SPLIT_EPI = false;
+    constexpr int DM = planes_dm(K16);
+#include "sl_planes64_step.inc"
+}
+
+// The kKeepC3 instances for a batch whose flag does not stand for both derived planes (DM 0:
+// all sixteen words stored, the code those instances were before derived planes): can_toggle_powers, a
+// pool with a bit-2 cell that lacks bit 15, a state built without the flag.  KIND: 0
+// k_env_step_bits64_planes<kKeepC3, OBS>, 1 k_env_planes64_gray<kKeepC3, OBS>, 2
+// k_env_planes64_w6, 3 k_env_planes64_s6, 4 k_env_planes64_chan<kKeepC3, obs_esz(OBS)>.
+// (One name apart from all of theirs: the resource tests count those by name.)
+constexpr int stored16_min_waves(int kind, int obs) {
+    return kind == 2 || kind == 3 ? kMinWavesW6 : (kind == 4 ? kMinWaves : planes_min_waves(kKeepC3, obs));
+}
+template <int KIND, int OBS>
+__global__ void __launch_bounds__(64, stored16_min_waves(KIND, OBS))
+k_env_p64_stored16(StepKArgs ka) {
+    constexpr u32 K16 = kKeepC3;
+    constexpr int DM = 0;
+    constexpr bool GRAY = KIND >= 1 && KIND <= 3, W6 = KIND == 2 || KIND == 3, SPLIT_EPI = KIND == 3;
+    __shared__ __attribute__((aligned(16))) u32 stage[W6 ? kStageDwW6 : N * N / 2];
+    __shared__ __attribute__((aligned(16))) uint16_t vmask[OBS >= 2 ? sl::obs::kFusedChanCells : 2];
+    uint16_t *const vm = OBS >= 2 ? vmask : nullptr;
 #include "sl_planes64_step.inc"
 }
 
@@ -1114,7 +1196,8 @@ __global__ void __launch_bounds__(64) k_board_sync64(sl_env_state st, int demote
     const int pok = __builtin_amdgcn_readfirstlane(st.planes_ok[b]);
     if (!(pok & SL_POK_BOARD_PLANES)) return;
     if (!(pok & SL_POK_BOARD_FULL)) {
-        const PlaneSlots<0> ps = PlaneSlots<0>::of(st.board_zero, st.agent_planes);
+        const PlaneSlots<0> ps = PlaneSlots<0>::of(st.board_zero, st.agent_planes,
+                                                   st.derived_planes);
         const u32 *bp = st.planes + b * 4096 + lane;
         u32 P[32];
 #pragma unroll
@@ -1126,6 +1209,22 @@ __global__ void __launch_bounds__(64) k_board_sync64(sl_env_state st, int demote
 #pragma unroll
         for (int q = 0; q < 32; q++)
             if ((ps.agent16() >> (q & 15)) & 1u) P[q] = aw[q >> 4];
+        // the derived planes: the crate's second bit, and the exits of the env's list
+        if (ps.drv16() & 0x8000u) {
+            PL(P, 15, 0) = PL(P, 2, 0);
+            PL(P, 15, 1) = PL(P, 2, 1);
+        }
+        if (ps.drv16() & 0x0100u) {
+            const int n = min(__builtin_amdgcn_readfirstlane(st.exit_count[b]), SL_MAX_EXITS);
+            PL(P, 8, 0) = PL(P, 8, 1) = 0u;
+            for (int e = 0; e < n; e++) {
+                const int y = __builtin_amdgcn_readfirstlane(st.exit_y[b * SL_MAX_EXITS + e]);
+                const int x = __builtin_amdgcn_readfirstlane(st.exit_x[b * SL_MAX_EXITS + e]);
+                const u32 bit = lane == 2 * (x >> 1) + (y >> 5) ? 1u << (y & 31) : 0u;
+                if (x & 1) PL(P, 8, 1) |= bit;
+                else PL(P, 8, 0) |= bit;
+            }
+        }
         transpose32(P);
         u32 *gb = reinterpret_cast<u32 *>(st.board + b * (int64_t)(N * N)) + (lane & 1) * 1024 +
                   (lane >> 1);
@@ -1287,12 +1386,42 @@ int counts64(const StepCall &c) {
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }
 
+// the kKeepC3 instance the plan names, for a plan without derived planes: its
+// k_env_p64_stored16 twin
+#define SL_STORED16(KIND, OBS) \
+    hipLaunchKernelGGL((k_env_p64_stored16<KIND, OBS>), dim3(grid), dim3(64), 0, s, ka)
+bool launch_stored16(const StepPlan &p, unsigned grid, const StepKArgs &ka, hipStream_t s) {
+    switch (p.kernel64) {
+    case SL_PLAN_K64_PLANES:
+        if (p.view_kind) SL_STORED16(0, 1);
+        else SL_STORED16(0, 0);
+        return true;
+    case SL_PLAN_K64_GRAY:
+        if (p.view_kind) SL_STORED16(1, 1);
+        else SL_STORED16(1, 0);
+        return true;
+    case SL_PLAN_K64_W6: SL_STORED16(2, 0); return true;
+    case SL_PLAN_K64_S6: SL_STORED16(3, 0); return true;
+    case SL_PLAN_K64_CHAN:
+        if (p.view_kind == 3) SL_STORED16(4, 3);
+        else if (p.view_kind == 4) SL_STORED16(4, 4);
+        else SL_STORED16(4, 2);
+        return true;
+    default: return false;
+    }
+}
+#undef SL_STORED16
+
 // the step kernel: the instance the plan names
 int step64(const StepCall &c) {
     const StepPlan &p = c.plan;
     const unsigned grid = (unsigned)c.st->B;
     const StepKArgs ka = kargs_of(c);
     hipStream_t s = c.s;
+    // the one place the derived planes choose a kernel: the plan's `derived` (both planes or
+    // none in the kKeepC3 class, whose instances have 0x8100 compiled in)
+    if (p.keep == SL_PLAN_KEEP_C3 && p.derived == 0 && launch_stored16(p, grid, ka, s))
+        return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
     switch (p.kernel64) {
     case SL_PLAN_K64_BITS64:
         if (p.replay) launch_bits64<SPAWN_STREAM>(p.view_kind, grid, ka, s);

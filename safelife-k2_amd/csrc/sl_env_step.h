@@ -52,7 +52,8 @@ const StepHooks &hooks_128();       // sl_bits128.hip
 
 // k_env_reset_scan over all envs: SL_PLAN_RESETS_SCAN (sl_env.hip)
 int reset_scan(const StepCall &c);
-// the SL_PLAN_KEEP_* class of a 64x64 plane state's board_zero / agent_planes (sl_bits.hip)
+// the SL_PLAN_KEEP_* class of a 64x64 plane state's board_zero / agent_planes (sl_bits.hip;
+// derived_planes is a run-time flag of every class)
 int planes64_keep(const sl_env_state &st);
 
 // host pieces of sl_env.hip the plan and the sequence use

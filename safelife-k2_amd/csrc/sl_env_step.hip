@@ -149,6 +149,11 @@ int sl::plan_step(const sl_env_state &st, const sl_level_pool *pool, const sl_en
         p.kernel64 = SL_PLAN_K64_BITS64;
     } else if (fast) {
         p.keep = planes64_keep(st);
+        // (the derived planes -- both or none -- make no class of their own: a C3 batch
+        // without them runs the same instances compiled to store all sixteen words)
+        const uint32_t laid = ~st.board_zero & ~st.agent_planes & 0xFFFFu;
+        p.derived = (int32_t)(((st.derived_planes & 0x8100u) == 0x8100u ? 0x8100u : 0u) & laid);
+        p.stored = (int32_t)(laid & ~(uint32_t)p.derived);
         const bool gray = p.keep == SL_PLAN_KEEP_C3 && st.goals_gray;
         if (p.view_kind >= 2) p.kernel64 = SL_PLAN_K64_CHAN;
         else if (!gray) p.kernel64 = SL_PLAN_K64_PLANES;

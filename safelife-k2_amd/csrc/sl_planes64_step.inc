@@ -1,6 +1,7 @@
 // sl_planes64_step.inc -- one plane-mode env-step of env blockIdx.x: the body of the
 // kernels k_env_step_bits64_planes and k_env_planes64_chan (sl_bits.hip), included inside
-// each.  (Text, not a force-inlined function: as a function templated on <K16, OBS> and
+// each, which sets DM, the derived planes the instance is compiled for (PlaneSlots).
+// (Text, not a force-inlined function: as a function templated on <K16, OBS> and
 // called from thin kernels, the same statements left k_env_step_bits64_planes<0x877F, 0>
 // with 3692 spilled VGPRs and 3112 B of scratch at its 96-register budget, and moved the
 // run-time-mask instances by two registers; included, the six older kernels compile to
@@ -24,13 +25,18 @@
     const int64_t b = blockIdx.x;          // one wave per env
     const int lane = threadIdx.x;
     lds_u32 *buf = (lds_u32 *)&stage[0];
-    const PlaneSlots<K16> ps = PlaneSlots<K16>::of(st.board_zero, st.agent_planes);
+    const PlaneSlots<K16, DM> ps = PlaneSlots<K16, DM>::of(st.board_zero, st.agent_planes,
+                                                           st.derived_planes);
     // what the buffer holds at one time: the stored plane words, the pool's start-plane
     // rows, or (W6) half a uint16 board
     constexpr int kStageDw = (int)(sizeof(stage) / sizeof(u32));
-    static_assert(!W6 || (PlaneSlots<K16>::kFixed && OBS == 0), "W6: fixed planes, no views");
-    static_assert(!W6 || 2 * __builtin_popcount(K16 & ~kAgentC3 & 0xFFFFu) * 64 <= kStageDw,
-                  "the stored plane words fit the buffer");
+    static_assert(!W6 || (PlaneSlots<K16, DM>::kFixed && OBS == 0), "W6: fixed planes, no views");
+    // the stored words: held, not the agent's, not derived (DM 0x8100: twelve, 3 KiB; the
+    // stored-16 twins: sixteen, 4 KiB)
+    constexpr int kStoredWords =
+        2 * __builtin_popcount(K16 & ~kAgentC3 & ~(u32)(DM > 0 ? DM : 0) & 0xFFFFu);
+    static_assert(K16 != kKeepC3 || kStoredWords == (DM ? 12 : 16), "three DMA groups, or four");
+    static_assert(!W6 || kStoredWords * 64 <= kStageDw, "the stored plane words fit the buffer");
     static_assert(pool_rows_dwords(K16 ? K16 : 0xFFFFu, W6) <= kStageDw,
                   "the pool's start-plane rows fit the buffer");
     static_assert(kStageDw >= (W6 ? N * N / 4 : N * N / 2), "a board, or half of one (W6)");
@@ -101,7 +107,7 @@
     u32 eval[4];
     const int ay0 = rec(V, R_AY), ax0 = rec(V, R_AX);
     // (cell 0 is the agent's: the agent planes' bits are there, and in no other cell)
-    const u32 near = lane < 9 ? lds_plane_cell(buf, ps, near_cell_index(lane, ay0, ax0)) |
+    const u32 near = lane < 9 ? lds_plane_cell(buf, ps, V, near_cell_index(lane, ay0, ax0)) |
                                     (lane == 0 ? ps.agent16() : 0u)
                               : 0u;
     OverlayT<NearCells> ov;
@@ -154,6 +160,18 @@
 #pragma unroll
         for (int q = 0; q < 32; q++)
             if ((ps.agent16() >> (q & 15)) & 1u) PB[q] = aw[q >> 4];
+    }
+    // the derived planes (PlaneSlots): plane 15 is plane 2 with the action's edits in it;
+    // plane 8 is the record's exit list (no action or rule moves, makes or removes an exit)
+    if (ps.drv16() & 0x8000u) {
+#pragma unroll
+        for (int w = 0; w < 2; w++) PL(PB, 15, w) = PL(PB, 2, w);
+    }
+    if (ps.drv16() & 0x0100u) {
+        u32 ew[2];
+        exit_words(V, lane, ew);
+#pragma unroll
+        for (int w = 0; w < 2; w++) PL(PB, 8, w) = ew[w];
     }
     // held: changed cells that held a plane a change clears but never sets
     u32 cb[2], held[2];

@@ -70,7 +70,8 @@ class EnvState(ctypes.Structure):
                 ("level_index", vp), ("episodes", vp), ("num_steps", vp),
                 ("spawn_flags", vp), ("start_roll", vp), ("planes", vp), ("planes_ok", vp),
                 ("elig_planes", vp), ("board_planes", vp), ("board_zero", u32),
-                ("planes_live", i32), ("agent_planes", u32), ("goals_gray", u32)]
+                ("planes_live", i32), ("agent_planes", u32), ("goals_gray", u32),
+                ("derived_planes", u32)]
 
 
 class LevelPool(ctypes.Structure):
@@ -99,7 +100,7 @@ class StepPlan(ctypes.Structure):
     """sl_step_plan: what sl_env_step would run (sl_env_step_plan; host only)."""
     _fields_ = [(n, i32) for n in ("empty", "family", "replay", "stream_phase", "plane_mode",
                                    "demote_first", "obs", "resets", "capture", "kernel64",
-                                   "keep", "view_kind")]
+                                   "keep", "view_kind", "stored", "derived")]
 
 
 class MT19937(ctypes.Structure):

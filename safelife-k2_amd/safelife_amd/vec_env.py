@@ -110,6 +110,34 @@ def goals_gray(goals):
     return int(bool(((r == gr) & (r == b)).all()))
 
 
+DERIVABLE_PLANE_BITS = 0x8100  # CellTypes: bit 15 (the crate's second bit) | exit
+
+
+def derived_planes(board, can_toggle_powers=False):
+    """sl_env_state.derived_planes for levels `board` [K, H, W]: the planes every board
+    holds that the 64x64 plane kernels rebuild instead of loading and storing them.
+    Bit 15: planes 2 and 15 agree in every cell of every level (only a crate carries
+    either), and powers cannot be toggled -- a toggle could give the agent bit 2 alone.
+    Actions move whole cells or write LIFE | colour and the rule clears both bits
+    together, so the planes stay equal.  Bit 8: every level has at most 8 exits, which is
+    what an env's exit list holds (SL_MAX_EXITS), and every exit is frozen and neither
+    pushable, pullable nor destructible; the list is then exactly the cells with the exit
+    bit, for good -- such an exit is never pushed, pulled, made or destroyed."""
+    b = np.asarray(board, dtype=np.uint16)
+    if b.shape[0] == 0:
+        return 0
+    mask = 0
+    if not can_toggle_powers and bool((((b >> 2) & 1) == ((b >> 15) & 1)).all()):
+        mask |= 0x8000
+    ex = b[(b & 0x0100) != 0]
+    # (an exit that is not frozen can be overwritten by a birth; one that is pushable,
+    # pullable or destructible -- 0x800C -- can be moved or removed by the action)
+    if (int(((b & 0x0100) != 0).reshape(b.shape[0], -1).sum(1).max()) <= 8
+            and bool(((ex & 0x0010) != 0).all()) and not bool((ex & 0x800C).any())):
+        mask |= 0x0100
+    return mask
+
+
 def start_board_hi_bits(start_board):
     """Per env: does any start-board cell use bits 12-14 (used by no cell type)?"""
     import torch
@@ -277,6 +305,7 @@ class SafeLifeVecEnv:
             s.board_zero = self._zero_planes(self._pool_bits(self.pool))
             s.agent_planes = self._agent_planes(self.pool)
             s.goals_gray = goals_gray(self.pool.goals)
+            s.derived_planes = self._derived_planes(self.pool)
         if (H, W) == (128, 128):
             # the 128x128 board in bit planes, kept there by steps without observations
             # or with packed views (sl_env_state.board_planes); `board` completes the
@@ -357,6 +386,24 @@ class SafeLifeVecEnv:
             s.agent_planes = new
             s.planes_live = 0
 
+    def _derived_planes(self, pool):
+        """sl_env_state.derived_planes that boards reset from `pool` keep."""
+        return derived_planes(pool.board, self.can_toggle_powers)
+
+    def _narrow_derived_planes(self, keep=0):
+        """Boards that keep only the derived planes `keep` are about to enter the batch (0:
+        a board written from outside, of which nothing is known): the others leave
+        derived_planes, never to return.  Envs kept in planes under the old mask are
+        completed and taken out of plane mode first, as in _narrow_agent_planes: the
+        planes leaving the mask were never stored."""
+        s = self._state
+        new = s.derived_planes & keep
+        if new != s.derived_planes:
+            self.sync_board()
+            self._pok_clear(_lib.SL_POK_BOARD)
+            s.derived_planes = new
+            s.planes_live = 0
+
     def _narrow_goals_gray(self, keep=0):
         """Goals are about to enter the batch that are all black or white (keep=1) or of
         which nothing is known (0: written from outside): goals_gray only ever narrows.
@@ -367,10 +414,12 @@ class SafeLifeVecEnv:
     def _admit_pool_boards(self, pool):
         """Resets are about to draw boards from `pool` (set_pool; a game's deserialize):
         their cell bits leave board_zero, agent planes their agents do not keep leave
-        agent_planes, coloured goals end goals_gray, and their spawners count.  Running
+        agent_planes, planes that do not follow from the rest of their state leave
+        derived_planes, coloured goals end goals_gray, and their spawners count.  Running
         envs keep their boards, so the spawner flag only grows here."""
         self._allow_board_bits(self._pool_bits(pool))
         self._narrow_agent_planes(self._agent_planes(pool))
+        self._narrow_derived_planes(self._derived_planes(pool))
         self._narrow_goals_gray(goals_gray(pool.goals))
         self._may_spawn = self._may_spawn or pool.has_spawners()
 
@@ -423,6 +472,7 @@ class SafeLifeVecEnv:
         v = self._cells(cells)
         self._allow_board_bits(self._device_board_bits(v))
         self._narrow_agent_planes()
+        self._narrow_derived_planes()
         self._synced_board()[e].copy_(v)
         self.st_t["spawn_flags"][e].bitwise_or_(1)      # may now hold a spawner
         self._may_spawn = True
@@ -891,8 +941,8 @@ class SafeLifeVecEnv:
         s.B, s.H, s.W = n, self.H, self.W
         for name, _ in _lib.EnvState._fields_[3:]:
             base = getattr(full, name)
-            if name in ("board_zero", "planes_live", "agent_planes",
-                        "goals_gray"):                        # (not per-env pointers)
+            if name in ("board_zero", "planes_live", "agent_planes", "goals_gray",
+                        "derived_planes"):                    # (not per-env pointers)
                 setattr(s, name, base)
                 continue
             if not base:
@@ -974,6 +1024,7 @@ class SafeLifeVecEnv:
         # (boards and agents written from outside: no plane is the agent's alone; every
         # env leaves plane mode below)
         self._state.agent_planes = 0
+        self._state.derived_planes = 0   # (nor does any plane follow from the others)
         self._narrow_goals_gray()        # (goals written from outside: of any colour)
         # may hold spawners (replay counts them); bit 2 (128x128 boards): the start board
         # uses cell bits 12-14, which the 128x128 kernel then compares in a second pass
@@ -1005,6 +1056,9 @@ class SafeLifeVecEnv:
         # batch's still are)
         d["goals_gray"] = self.torch.tensor(int(self._state.goals_gray),
                                             dtype=self.torch.int32)
+        # the derived planes these boards keep (as agent_planes)
+        d["derived_planes"] = self.torch.tensor(int(self._state.derived_planes),
+                                                dtype=self.torch.int32)
         return d
 
     def load_state_dict(self, d):
@@ -1032,6 +1086,8 @@ class SafeLifeVecEnv:
         # less what outside writes took); a dict without the entry keeps none
         ap = self._state.agent_planes & int(d.get("agent_planes", 0))
         gg = self._state.goals_gray & int(d.get("goals_gray", 0))
+        dp = self._state.derived_planes & int(d.get("derived_planes", 0))
         self._invalidate_caches()
         self._state.agent_planes = ap
         self._state.goals_gray = gg
+        self._state.derived_planes = dp
