@@ -31,6 +31,7 @@
 // instantiation also writes the packed observation (write_obs, 130 VGPRs, 3 waves).
 #include "sl_bits_geo.h"
 #include "sl_env_step.h"
+#include "sl_action4.h"
 
 using namespace sl;
 using namespace sl::fast;
@@ -233,6 +234,27 @@ __device__ __forceinline__ u32 mux_edits(u32 P[32], int ne, const int eidx[4], c
         }
     }
     return erow;
+}
+// The same for the plane step's four fixed slots (sl_action4.h): slot k is written where bit
+// k of `changed` is set; the four cells are distinct, so the order does not matter.
+__device__ __forceinline__ void mux_edits4(u32 P[32], u32 changed, const int eidx[4],
+                                           const u32 eval[4], int lane) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if ((changed >> k) & 1u) {
+            const int y = eidx[k] >> 6, x = eidx[k] & 63;
+            const int tl = 2 * (x >> 1) + (y >> 5);            // lane holding the cell
+            const u32 bit = 1u << (y & 31);
+            const u32 m0 = (lane == tl && !(x & 1)) ? bit : 0u;
+            const u32 m1 = (lane == tl && (x & 1)) ? bit : 0u;
+#pragma unroll
+            for (int p = 0; p < 16; p++) {
+                const u32 v = ((eval[k] >> p) & 1u) ? ~0u : 0u;
+                PL(P, p, 0) = mux(m0, v, PL(P, p, 0));
+                PL(P, p, 1) = mux(m1, v, PL(P, p, 1));
+            }
+        }
+    }
 }
 
 // SafeLifeEnv.reset (safelife_env.py:188-198) of env b by one wave, right after the
@@ -1029,6 +1051,27 @@ __device__ __forceinline__ u32 lds_plane_cell(const lds_u32 *buf, PlaneSlots<K16
         for (int e = 0; e < n; e++)
             if (i == fl.exit_y(e) * 64 + fl.exit_x(e)) v |= 0x0100u;
     }
+    return v;
+}
+
+// Cell i from the staged planes: its stored planes' bits, and plane 15 rebuilt from plane 2
+// where it is derived (the action moves crates whole).  Not in the value: the agent planes
+// (the caller adds them to the agent's cell) and a derived exit plane (the caller takes the
+// bit from the record's exit list).  Every lane may read its own cell.
+template <u32 K16, int DM>
+__device__ __forceinline__ u32 lds_plane_cell_stored(const lds_u32 *buf, PlaneSlots<K16, DM> ps,
+                                                     int i) {
+    const int y = i >> 6, x = i & 63;
+    const lds_u32 *q = buf + 2 * (x >> 1) + (y >> 5);
+    const u32 r = (u32)(y & 31);
+    const int w = 16 * (x & 1);
+    u32 v = 0;
+#pragma unroll
+    for (int p = 0; p < 16; p++) {
+        const int pw = ps.pos(p) + (w ? ps.stored16() : 0);
+        if (ps.stored(p)) v |= ((q[pw * 64] >> r) & 1u) << p;
+    }
+    if (ps.drv16() & 0x8000u) v |= (v & 4u) << 13;
     return v;
 }
 

@@ -80,6 +80,46 @@
 
     int roll = -1;
     if (fx.pool.K > 0 && fx.pool.board_planes && st.start_roll) roll = rec(V, R_ROLL);
+    // The action reads four cells -- the agent's, the one in front, the one behind, the one
+    // two ahead (sl_action4.h) -- and which four is in the record: their indices, the exits
+    // among them and can_exit are worked out while the planes are in flight.  (ACT4: the
+    // instances with compile-time plane masks.  Those with run-time masks, K16 == 0, keep
+    // act_core on a nine-cell gather: with this form k_env_planes64_chan<0, *> and
+    // k_env_step_bits64_planes<0, 1> gained 68 B of scratch per lane.)
+    constexpr bool ACT4 = K16 != 0;
+    static_assert(N >= 5 && (N & (N - 1)) == 0, "the four cells are distinct; wrapped by mask");
+    const int act = rec(V, R_ACT), go0 = rec(V, R_GO);
+    const int ay0 = rec(V, R_AY), ax0 = rec(V, R_AX);
+    int eidx[4] = {0, 0, 0, 0};     // the edited cells' flat indices
+    int cell_i = 0;                 // (ACT4) this lane's cell: cell lane & 3
+    u32 exit_hits = 0u;             // (ACT4) bit k + 4 e: cell k is exit e of the record's list
+    bool can_exit0 = false;
+    if (ACT4) {
+        const int orient = (act - 1) & 3;
+        const int fdx = orient == 1 ? 1 : (orient == 3 ? -1 : 0);
+        const int fdy = orient == 0 ? -1 : (orient == 2 ? 1 : 0);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int d = k == 2 ? -1 : (k == 3 ? 2 : k);
+            eidx[k] = ((ay0 + d * fdy) & (N - 1)) * N + ((ax0 + d * fdx) & (N - 1));
+        }
+        cell_i = (lane & 2) ? ((lane & 1) ? eidx[3] : eidx[2])
+                            : ((lane & 1) ? eidx[1] : eidx[0]);
+        // lane k + 4 e compares cell k with exit e (the derived exit plane has no words to
+        // gather the bit from)
+        if (ps.drv16() & 0x0100u) {
+            const int e = (lane >> 2) & 7;
+            const int sh = 16 * (e & 1);
+            const int ey = (int)(int16_t)(
+                __builtin_amdgcn_ds_bpermute(4 * (R_EY + (e >> 1)), (int)V) >> sh);
+            const int ex = (int)(int16_t)(
+                __builtin_amdgcn_ds_bpermute(4 * (R_EX + (e >> 1)), (int)V) >> sh);
+            const int n = min(rec(V, R_EXC), SL_MAX_EXITS);
+            exit_hits = (u32)__ballot(lane < 32 && e < n && ey * N + ex == cell_i);
+        }
+        can_exit0 = can_exit_now(rec_f64(V, R_MP), rec(V, R_SCORE), rec(V, R_BASE),
+                                 rec(V, R_POSS));
+    }
     wait_vm();
     if (!pin) {
         // a step into plane mode: the uint16 board instead, transposed and put into the
@@ -98,48 +138,79 @@
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    // the action (lane 0) on the cells round the agent, gathered from the staged planes
-    // (kept copy of step_env's prologue: see there)
-    RecEnv env{st, b, rec(V, R_GO), rec(V, R_AX), rec(V, R_AY), rec(V, R_SCORE),
-               rec(V, R_BASE), rec(V, R_POSS), rec_f64(V, R_MP)};
-    int act_reward = 0;
-    int eidx[4];
+    int act_reward = 0, go1 = go0, ax1 = ax0, ay1 = ay0;    // ..1: after the action
+    u32 echg = 0u;                  // bit k: cell eidx[k] becomes eval[k]
     u32 eval[4];
-    const int ay0 = rec(V, R_AY), ax0 = rec(V, R_AX);
-    // (cell 0 is the agent's: the agent planes' bits are there, and in no other cell)
-    const u32 near = lane < 9 ? lds_plane_cell(buf, ps, V, near_cell_index(lane, ay0, ax0)) |
-                                    (lane == 0 ? ps.agent16() : 0u)
-                              : 0u;
-    OverlayT<NearCells> ov;
-    ov.src = NearCells{ay0, ax0, near};
-    ov.n = 0;
+    if (ACT4) {
+        // wave-uniform: every lane reads its cell's stored planes (four addresses,
+        // broadcast), lanes 0-3 hand the four cells to scalars, action4 decides; four fixed
+        // slots of edits, in any order (the cells are distinct)
+        const u32 cell_v = lds_plane_cell_stored(buf, ps, cell_i);
+        u32 cell[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        ov.idx[k] = 0;
-        ov.val[k] = 0;
+        for (int k = 0; k < 4; k++) {
+            cell[k] = (u32)__builtin_amdgcn_readlane((int)cell_v, k);
+            if ((ps.drv16() & 0x0100u) && (exit_hits & (0x11111111u << k))) cell[k] |= EXIT;
+        }
+        // (the agent planes' bits are in the agent's cell, and in no other)
+        cell[0] |= ps.agent16();
+        const act4::Result ar = act4::action4(act, go0, can_exit0, ka.ctp, ka.ctc, cell[0],
+                                              cell[1], cell[2], cell[3]);
+        act_reward = ar.reward;
+        go1 = ar.game_over;
+        if (ar.moved) {
+            ax1 = eidx[1] & (N - 1);
+            ay1 = eidx[1] / N;
+        }
+        if (lane == 0) {
+            if (ar.store_orient) st.orientation[b] = ar.orient;
+            if (ar.reward) st.game_over[b] = 1;
+            if (ar.store_agent) {
+                st.agent_x[b] = ax1;
+                st.agent_y[b] = ay1;
+            }
+        }
+        echg = ar.changed;
+#pragma unroll
+        for (int k = 0; k < 4; k++) eval[k] = ar.n[k];
+    } else {
+        // lane 0, on the cells round the agent gathered from the staged planes (kept copy
+        // of step_env's prologue: see there); its counted edits fill the first slots
+        RecEnv env{st, b, go0, ax0, ay0, rec(V, R_SCORE), rec(V, R_BASE), rec(V, R_POSS),
+                   rec_f64(V, R_MP)};
+        // (cell 0 is the agent's: the agent planes' bits are there, and in no other cell)
+        const u32 near = lane < 9 ? lds_plane_cell(buf, ps, V, near_cell_index(lane, ay0, ax0)) |
+                                        (lane == 0 ? ps.agent16() : 0u)
+                                  : 0u;
+        OverlayT<NearCells> ov;
+        ov.src = NearCells{ay0, ax0, near};
+        ov.n = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            ov.idx[k] = 0;
+            ov.val[k] = 0;
+        }
+        if (lane == 0) act_reward = act_core(env, act, N, N, ka.ctp, ka.ctc, ov);
+        act_reward = __builtin_amdgcn_readfirstlane(act_reward);
+        echg = (1u << __builtin_amdgcn_readfirstlane(ov.n)) - 1u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            eidx[k] = __builtin_amdgcn_readfirstlane(ov.idx[k]);
+            eval[k] = (u32)__builtin_amdgcn_readfirstlane((int)ov.val[k]);
+        }
+        go1 = __builtin_amdgcn_readfirstlane(env.go);
+        ax1 = __builtin_amdgcn_readfirstlane(env.ax);
+        ay1 = __builtin_amdgcn_readfirstlane(env.ay);
     }
-    if (lane == 0) act_reward = act_core(env, rec(V, R_ACT), N, N, ka.ctp, ka.ctc, ov);
-    int ne = ov.n;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        eidx[k] = ov.idx[k];
-        eval[k] = ov.val[k];
-    }
-    act_reward = __builtin_amdgcn_readfirstlane(act_reward);
-    ne = __builtin_amdgcn_readfirstlane(ne);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        eidx[k] = __builtin_amdgcn_readfirstlane(eidx[k]);
-        eval[k] = (u32)__builtin_amdgcn_readfirstlane((int)eval[k]);
         // no cell of the batch holds a bit outside the kept planes (board_zero), an
         // edited one included: said here, the planes not kept stay constants below
         if (K16) eval[k] &= K16;
         // the agent planes are rebuilt from the agent's new position below
         eval[k] &= ~ps.agent16();
     }
-    const RecFields fl = rec_fields(a, V, __builtin_amdgcn_readfirstlane(env.go),
-                                    __builtin_amdgcn_readfirstlane(env.ax),
-                                    __builtin_amdgcn_readfirstlane(env.ay));
+    const RecFields fl = rec_fields(a, V, go1, ax1, ay1);
 
     u32 PB[32];
 #pragma unroll
@@ -150,7 +221,7 @@
     if (roll < 0) {
         if (!W6) dma_board(st.start_board + off, buf, lane);
     } else pool_dma<KEEP, W6>(fx.pool, rec(V, R_LI), buf, lane);
-    (void)mux_edits(PB, ne, eidx, eval, lane);
+    mux_edits4(PB, echg, eidx, eval, lane);
     // the agent planes: one word pair, the bit of the agent's cell after the action (the
     // rule changes no such cell: the host puts a plane in agent_planes only where the
     // agent's cell is frozen), read by the rule and the views, never loaded or stored
@@ -229,7 +300,7 @@
     u32 em[2] = {0u, 0u};           // the words the action's edits touched (this lane's)
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        if (k < ne) {
+        if ((echg >> k) & 1u) {
             const int y = eidx[k] >> 6, x = eidx[k] & 63;
             const u32 bit = lane == 2 * (x >> 1) + (y >> 5) ? 1u << (y & 31) : 0u;
             em[x & 1] |= bit;
