@@ -103,6 +103,15 @@ extern "C" {
  * epilogue in the wave and the reset list, where the default splits them off */
 #define SL_PLANES64_W6_UNSPLIT (-6)
 
+/* sl_env_cfg.obs_fuse bits: views the step kernel is asked to write beyond its defaults.
+ * SL_OBS_FUSE_CHAN128: the 128x128 step kernel also writes channel views (SL_OBS_CHANNELS*)
+ * from the board planes, so the board stays in planes over such steps.  Taken only for a
+ * view of at most 96 rows, 128 columns and SL_FUSE_CHAN128_MAX_CELLS cells (the writer of the
+ * reset envs' views stages one env's view in LDS) into a 16-byte aligned obs_out; any other
+ * view is the observation kernel's, as with the bit clear.  Every other family ignores it. */
+#define SL_OBS_FUSE_CHAN128 1
+#define SL_FUSE_CHAN128_MAX_CELLS 4096
+
 #define SL_MAX_EXITS 8      /* exits tracked per env (benchmark levels have 1) */
 #define SL_BONUS_PERIOD_MAX 16
 
@@ -517,7 +526,8 @@ typedef struct sl_env_state {
                                  32t..32t+31).  When set, a step of the fast
                                  kernel without capture -- Philox or replay with
                                  draw planes; no obs_out, or packed views of at
-                                 most 96 rows, which it writes from the planes;
+                                 most 96 rows (with SL_OBS_FUSE_CHAN128 also
+                                 channel views), which it writes from the planes;
                                  sl_env_cfg.board_mode SL_BOARD_AUTO -- keeps
                                  the board here (SL_POK_BOARD_PLANES) and writes of
                                  the uint16 board only its band-edge rows (32t,
@@ -773,7 +783,13 @@ typedef struct sl_env_cfg {
                                        channel views of at most 64x64 and 1094
                                        cells into a 16-byte aligned obs_out, from
                                        the board they hold on chip (no re-read;
-                                       in plane mode from the planes, which stay) */
+                                       in plane mode from the planes, which stay).
+                                       The 128x128 kernel writes packed views of at
+                                       most 96 rows from the board planes, and with
+                                       obs_fuse & SL_OBS_FUSE_CHAN128 channel views
+                                       of at most 96 rows and
+                                       SL_FUSE_CHAN128_MAX_CELLS cells into a
+                                       16-byte aligned obs_out                  */
     int32_t obs_mode, obs_vh, obs_vw, obs_remove_white, obs_nch;
     int32_t obs_channels[16];
     const sl_capture *capture;      /* host pointer or NULL: trajectory capture
@@ -815,6 +831,7 @@ typedef struct sl_env_cfg {
                                        SL_PLANES64_W6_UNSPLIT keeps the six-wave
                                        kernel with the epilogue in the wave and the
                                        reset list (same results; for comparison) */
+    int32_t obs_fuse;               /* SL_OBS_FUSE_* bits; 0: the defaults     */
 } sl_env_cfg;
 
 /*
@@ -845,7 +862,10 @@ int sl_env_step_family(int H, int W, int kernel);
 /* sl_step_plan.obs: who writes the step's views */
 #define SL_PLAN_OBS_NONE 0
 #define SL_PLAN_OBS_FUSED64 1    /* the 64x64 step kernel (and its reset list)          */
-#define SL_PLAN_OBS_FUSED128 2   /* the 128x128 step kernel, then the reset envs' views */
+#define SL_PLAN_OBS_FUSED128 2   /* the 128x128 step kernel, then the reset envs' views:
+                                    packed views (k_env_step_bits128_view), or with
+                                    SL_OBS_FUSE_CHAN128 channel views (view_kind 2-4:
+                                    k_env_bits128_chan), both from the board planes     */
 #define SL_PLAN_OBS_SEPARATE 3   /* the observation kernel over all envs, after resets  */
 /* sl_step_plan.resets: who resets the finished envs */
 #define SL_PLAN_RESETS_NONE 0

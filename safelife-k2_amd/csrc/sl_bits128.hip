@@ -279,6 +279,106 @@ __device__ __forceinline__ const Step128KArgs &kargs128() {
 // (kViewMaxRows128) meets each band in one run of view rows.  Exits are rewritten after the epilogue
 // (view_exits), where their colour is decided.
 
+// ---- channel views from the same staged rows (SL_OBS_FUSE_CHAN128).  Element (cell i,
+// channel k) of env b is bit ch[k] of view cell i, stored as 0 / fx.obs_one in ESZ bytes
+// at byte ((b nv + i) nch + k) ESZ of obs_out (16-byte aligned).  The band's view rows
+// [va, vb) are one contiguous byte range [r0, r1) of it, in general aligned to ESZ only
+// (an env's view is 15 x 15 x 15 x 2 = 6 750 bytes, a view row 450): the 16-byte chunks
+// that lie whole within the range are stored as vectors, lane l taking the chunks l,
+// l + 64, ... (each store instruction one 1 KiB run), and the fewer than 16 bytes before
+// the first and after the last chunk element by element (lanes 0-15 and 32-47).  A
+// chunk that straddles two bands' ranges is thus written by both, each its own elements,
+// and no byte outside [r0, r1) -- so none outside the env's view -- is touched.  A chunk's
+// 16 / ESZ element bits are gathered from the channel masks of its cells (obs::ChanMap),
+// read from the staged rows at (row, column) kept per lane and advanced without a division.
+template <int ESZ>
+__device__ __forceinline__ void chan_rows_store(const lds_u16 *cells, int va, int vb, int vh,
+                                                int vw, int rofs, int tx, const obs::ChanMap &cm,
+                                                u32 one, int64_t b, uint8_t *__restrict__ out) {
+    const int nch = cm.nch, lane = lane_now();
+    const bool id = cm.ident();
+    const int64_t env0 = b * (int64_t)(vh * vw) * nch * ESZ;       // the env's first byte
+    const int64_t r0 = env0 + (int64_t)(va * vw) * nch * ESZ;
+    const int64_t r1 = env0 + (int64_t)(vb * vw) * nch * ESZ;
+    const int64_t c0 = (r0 + 15) & ~(int64_t)15, c1 = r1 & ~(int64_t)15;
+    // the channel mask of view cell (r, c): view row r in [va, vb) is the band's row
+    // (r + rofs) mod 128, one of its 32 (the index stays within the staged 8 KiB)
+    auto mask_at = [&](int r, int c) -> u32 {
+        return cm.mask((u32)cells[((r + rofs) & 31) * N + ((c + tx) & (N - 1))], id);
+    };
+    // the partial chunks at both ends: one element per lane
+    const int head = (int)(((c0 < r1 ? c0 : r1) - r0) / ESZ);
+    const int tail = c1 >= c0 ? (int)((r1 - c1) / ESZ) : 0;
+    int e = -1;                                 // element of the env's view (<= 2^16 of them)
+    if (lane < head) e = (int)((r0 - env0) / ESZ) + lane;
+    else if (lane >= 32 && lane - 32 < tail) e = (int)((c1 - env0) / ESZ) + (lane - 32);
+    if (e >= 0) {
+        const int cell = e / nch, k = e - cell * nch;
+        const int r = cell / vw, c = cell - r * vw;
+        const u32 v = ((mask_at(r, c) >> k) & 1u) ? one : 0u;
+        uint8_t *o = out + env0 + (int64_t)e * ESZ;
+        if (ESZ == 1) *o = (uint8_t)v;
+        else if (ESZ == 2) *reinterpret_cast<uint16_t *>(o) = (uint16_t)v;
+        else *reinterpret_cast<u32 *>(o) = v;
+    }
+    if (c1 <= c0) return;                       // (wave-uniform)
+    // whole chunks; a lane's next chunk starts 1024 / ESZ elements on: dcell cells (dr
+    // rows, dc columns) and dk channels
+    constexpr int NE = 16 / ESZ, STEP = 1024 / ESZ;
+    const int dcell = STEP / nch, dk = STEP - dcell * nch;
+    const int dr = dcell / vw, dc = dcell - dr * vw;
+    int k0, r, c;
+    {
+        const int e0 = (int)((c0 - env0) / ESZ) + lane * NE;
+        const int cell0 = e0 / nch;
+        k0 = e0 - cell0 * nch;
+        r = cell0 / vw;
+        c = cell0 - r * vw;
+    }
+    for (int64_t q = c0 + 16 * (int64_t)lane; q < c1; q += 16 * 64) {
+        u32 bits = mask_at(r, c) >> k0;         // the chunk's NE element bits, low bit first
+        int have = nch - k0, rr = r, cc = c;
+        while (have < NE) {
+            if (++cc == vw) {
+                cc = 0;
+                rr++;
+            }
+            bits |= mask_at(rr, cc) << have;
+            have += nch;
+        }
+        k0 += dk;
+        c += dc;
+        r += dr;
+        if (k0 >= nch) {
+            k0 -= nch;
+            c++;
+        }
+        if (c >= vw) {
+            c -= vw;
+            r++;
+        }
+        u32 wv[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (ESZ == 1)        // 4 bits -> 4 bytes
+                wv[j] = ((((bits >> (4 * j)) & 15u) * 0x00204081u) & 0x01010101u) * one;
+            else if (ESZ == 2)   // 2 bits -> 2 halfwords
+                wv[j] = ((((bits >> (2 * j)) & 3u) * 0x8001u) & 0x00010001u) * one;
+            else                 // 1 bit -> 1 word
+                wv[j] = ((bits >> j) & 1u) * one;
+        }
+        typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 v4 = {wv[0], wv[1], wv[2], wv[3]};
+        __builtin_nontemporal_store(v4, reinterpret_cast<u32x4 *>(out + q));
+    }
+}
+
+// the element bytes of a channel mode (wave-uniform)
+__device__ __forceinline__ int chan_esz(int mode) {
+    return mode == SL_OBS_CHANNELS_U8 ? 1 : (mode == SL_OBS_CHANNELS_F32 ? 4 : 2);
+}
+
+template <bool CHAN>
 __device__ __forceinline__ void view_band(u32 P[32], const u32 gcol[3][2], int t, int agy,
                                           int agx, __attribute__((address_space(3))) u32 *spool,
                                           int64_t b) {
@@ -322,6 +422,15 @@ __device__ __forceinline__ void view_band(u32 P[32], const u32 gcol[3][2], int t
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const lds_u16 *cells = (const lds_u16 *)spool;
+    if (CHAN) {
+        const obs::ChanMap cm{k.fx.obs_chpack, k.fx.obs_nch};
+        uint8_t *o8 = reinterpret_cast<uint8_t *>(k.fx.obs_out);
+        const int esz = chan_esz(k.fx.obs_mode), rofs = ty - 32 * t;
+        if (esz == 1) chan_rows_store<1>(cells, va, vb, vh, vw, rofs, tx, cm, k.fx.obs_one, b, o8);
+        else if (esz == 4) chan_rows_store<4>(cells, va, vb, vh, vw, rofs, tx, cm, k.fx.obs_one, b, o8);
+        else chan_rows_store<2>(cells, va, vb, vh, vw, rofs, tx, cm, k.fx.obs_one, b, o8);
+        return;
+    }
     uint16_t *o = k.fx.obs_out + b * (int64_t)(vh * vw);
     const int i_end = vb * vw, dr = 64 / vw, dc = 64 - dr * vw;
     int i = va * vw + lane;
@@ -373,12 +482,29 @@ __device__ __forceinline__ ViewExit view_exits_load(const sl_env_state &st, int6
     }
     return ve;
 }
+// (the channel form: the nch elements of the target cell)
+template <bool CHAN>
 __device__ __forceinline__ void view_exits_store(const ViewExit &ve, int64_t b, int can) {
     const Step128KArgs &k = kargs128();
     if (ve.tgt < 0) return;
     const u32 ev = LEVEL_EXIT | (can ? COLOR_R : 0u);
-    k.fx.obs_out[b * (int64_t)(k.fx.obs_vh * k.fx.obs_vw) + ve.tgt] =
-        obs::obs_value(ev, ve.goal & 0xFFFFu, k.fx.obs_rw);
+    const u32 v = obs::obs_value(ev, ve.goal & 0xFFFFu, k.fx.obs_rw);
+    const int64_t cell = b * (int64_t)(k.fx.obs_vh * k.fx.obs_vw) + ve.tgt;
+    if (!CHAN) {
+        k.fx.obs_out[cell] = (uint16_t)v;
+        return;
+    }
+    const int nch = k.fx.obs_nch, esz = chan_esz(k.fx.obs_mode);
+    const uint64_t chpack = k.fx.obs_chpack;
+    const u32 one = k.fx.obs_one;
+    uint8_t *o8 = reinterpret_cast<uint8_t *>(k.fx.obs_out);
+    for (int j = 0; j < nch; j++) {
+        const u32 x = ((v >> ((chpack >> (4 * j)) & 15u)) & 1u) ? one : 0u;
+        const int64_t e = cell * nch + j;
+        if (esz == 1) o8[e] = (uint8_t)x;
+        else if (esz == 4) reinterpret_cast<u32 *>(o8)[e] = x;
+        else reinterpret_cast<uint16_t *>(o8)[e] = (uint16_t)x;
+    }
 }
 
 // One env-step of env b, after the action: k_env_action has applied it -- state and cell edits in HBM, reward
@@ -392,8 +518,10 @@ __device__ __forceinline__ void view_exits_store(const ViewExit &ve, int64_t b, 
 // 10 of 16 planes, 37 % fewer plane bytes)
 constexpr u32 kKeep128All = 0xFFFFu, kKeep128C5 = 0x07FBu;
 
-template <int MODE, bool VIEW, u32 KEEP>
+// VIEWS: 0 no views, 1 packed views, 2 channel views, written from the planes
+template <int MODE, int VIEWS, u32 KEEP>
 __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
+    constexpr bool VIEW = VIEWS != 0, CHAN = VIEWS == 2;
     const sl_env_state &st = ka.st;
     const StepArgs &a = ka.a;
     const FastExtra &fx = ka.fx;
@@ -749,7 +877,7 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
                 if (VIEW) transpose32(P);        // (a step into plane mode: planes again)
             }
         }
-        if (VIEW) view_band(P, gcol, t, agy, agx, spool, b);
+        if (VIEW) view_band<CHAN>(P, gcol, t, agy, agx, spool, b);
     }
     if (MODE == SPAWN_DECIDED) {
         u32 E0[8];
@@ -790,30 +918,43 @@ __device__ __forceinline__ void step128_body(const Step128KArgs &ka) {
         if (k.fx.fuse_reset && reset) queue_reset(k.fx.scratch, k.st.B, k.a.step, b);
     }
     // (the view's band stores have completed: wait_vm above)
-    if (VIEW) view_exits_store(vex, b, __builtin_amdgcn_readfirstlane(can));
+    if (VIEW) view_exits_store<CHAN>(vex, b, __builtin_amdgcn_readfirstlane(can));
 }
 
 // the step kernel: Philox, the stream fallback or decided replay; no views
 template <int MODE, u32 KEEP>
 __global__ void __launch_bounds__(64, MODE == SPAWN_STREAM ? kMinWavesStream : kMinWaves)
 k_env_step_bits128(Step128KArgs ka) {
-    step128_body<MODE, false, KEEP>(ka);
+    step128_body<MODE, 0, KEEP>(ka);
 }
 
 // ... with packed views written from the planes (plane mode, fx.obs_out)
 template <int MODE, u32 KEEP>
 __global__ void __launch_bounds__(64, kMinWaves)
 k_env_step_bits128_view(Step128KArgs ka) {
-    step128_body<MODE, true, KEEP>(ka);
+    step128_body<MODE, 1, KEEP>(ka);
+}
+
+// ... with channel views written from the planes (SL_OBS_FUSE_CHAN128; the element size
+// is a wave-uniform branch round the store loop, so one instance serves u8, u16 / bf16
+// and f32)
+template <int MODE, u32 KEEP>
+__global__ void __launch_bounds__(64, kMinWaves)
+k_env_bits128_chan(Step128KArgs ka) {
+    step128_body<MODE, 2, KEEP>(ka);
 }
 
 // the instance for a plane-mode launch: the C5 planes when no board can hold another
 template <int MODE>
-void launch_step128(const Step128KArgs &ka, bool view, hipStream_t s) {
+void launch_step128(const Step128KArgs &ka, bool view, bool chan, hipStream_t s) {
     const dim3 grid((unsigned)ka.st.B);
     const u32 keep = ~ka.st.board_zero & 0xFFFFu;
     const bool c5 = ka.fx.plane_mode && !(keep & ~kKeep128C5);
-    if (view && c5)
+    if (chan && c5)
+        hipLaunchKernelGGL((k_env_bits128_chan<MODE, kKeep128C5>), grid, dim3(64), 0, s, ka);
+    else if (chan)
+        hipLaunchKernelGGL((k_env_bits128_chan<MODE, kKeep128All>), grid, dim3(64), 0, s, ka);
+    else if (view && c5)
         hipLaunchKernelGGL((k_env_step_bits128_view<MODE, kKeep128C5>), grid, dim3(64), 0, s, ka);
     else if (view)
         hipLaunchKernelGGL((k_env_step_bits128_view<MODE, kKeep128All>), grid, dim3(64), 0, s, ka);
@@ -1461,10 +1602,11 @@ int pre_step128(const StepCall &c) {
 int step128(const StepCall &c) {
     const Step128KArgs ka = kargs_of(c);
     const bool views = c.plan.obs == SL_PLAN_OBS_FUSED128;
+    const bool chan = views && c.plan.view_kind >= 2;
     if (!c.plan.replay)
-        launch_step128<SPAWN_PHILOX>(ka, views, c.s);
+        launch_step128<SPAWN_PHILOX>(ka, views, chan, c.s);
     else if (c.st->elig_planes)
-        launch_step128<SPAWN_DECIDED>(ka, views, c.s);
+        launch_step128<SPAWN_DECIDED>(ka, views, chan, c.s);
     else
         hipLaunchKernelGGL((k_env_step_bits128<SPAWN_STREAM, kKeep128All>), dim3((unsigned)c.st->B),
                            dim3(64), 0, c.s, ka);

@@ -730,6 +730,21 @@ k_env_obs_channels(sl_env_state st, ObsArgs a, uint64_t chpack, uint32_t one, in
                            obs_lds + wid * vpad, out);
 }
 
+// ... and their channel views (SL_OBS_FUSE_CHAN128: the step kernel wrote the others'),
+// by the same wave writer; LDS as k_env_obs_channels
+template <int ESZ>
+__global__ void __launch_bounds__(256)
+k_env_obs_reset_list_chan(sl_env_state st, ObsArgs a, uint64_t chpack, uint32_t one, int vpad,
+                          const int64_t *scratch, uint32_t step, uint8_t *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) uint16_t obs_lds[];
+    const int n = (int)scratch[8 * st.B + 2 + (step & 1)];
+    const int32_t *list = reset_list(const_cast<int64_t *>(scratch));
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (int i = blockIdx.x * 4 + wid; i < n; i += gridDim.x * 4)
+        obs_channels_wave<ESZ>(st, a, ChanMap{chpack, a.nch}, one, list[i], threadIdx.x & 63,
+                               obs_lds + wid * vpad, out);
+}
+
 bool set_lds(const void *fn, size_t bytes) {
     if (bytes <= 65536) return true;
     return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) ==
@@ -822,10 +837,33 @@ int launch_env_action(const sl_env_state &st, const int32_t *actions, int ctp, i
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }
 
-int launch_obs_reset_list(const sl_env_state &st, const ObsArgs &a, uint16_t *out,
+int launch_obs_reset_list(const sl_env_state &st, const ObsArgs &a, void *out,
                           const int64_t *scratch, uint32_t step, hipStream_t s) {
     const unsigned grid = (unsigned)(st.B < 1024 ? (st.B + 3) / 4 : 256);
-    hipLaunchKernelGGL(k_env_obs_reset_list, dim3(grid), dim3(256), 0, s, st, a, scratch, step, out);
+    if (a.mode == SL_OBS_PACKED) {
+        hipLaunchKernelGGL(k_env_obs_reset_list, dim3(grid), dim3(256), 0, s, st, a, scratch, step,
+                           (uint16_t *)out);
+        return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
+    }
+    // channel views: the wave writer of launch_obs, within its limits (the plan's)
+    const int nv = a.vh * a.vw;
+    if ((((uintptr_t)out) & 15) != 0 || nv > kObsMaxCells) return SL_EINVAL;
+    uint64_t chpack = 0;
+    for (int k = 0; k < a.nch; k++) chpack |= (uint64_t)a.ch[k] << (4 * k);
+    const uint32_t one = a.mode == SL_OBS_CHANNELS_F32 ? 0x3F800000u
+                         : a.mode == SL_OBS_CHANNELS_BF16 ? 0x3F80u : 1u;
+    const int vpad = (nv + 2 + 7) & ~7;
+    const size_t lds = (size_t)4 * vpad * sizeof(uint16_t);
+    uint8_t *o = (uint8_t *)out;
+    if (a.mode == SL_OBS_CHANNELS_U8)
+        hipLaunchKernelGGL(k_env_obs_reset_list_chan<1>, dim3(grid), dim3(256), lds, s, st, a,
+                           chpack, one, vpad, scratch, step, o);
+    else if (a.mode == SL_OBS_CHANNELS_F32)
+        hipLaunchKernelGGL(k_env_obs_reset_list_chan<4>, dim3(grid), dim3(256), lds, s, st, a,
+                           chpack, one, vpad, scratch, step, o);
+    else
+        hipLaunchKernelGGL(k_env_obs_reset_list_chan<2>, dim3(grid), dim3(256), lds, s, st, a,
+                           chpack, one, vpad, scratch, step, o);
     return hipGetLastError() == hipSuccess ? SL_OK : SL_EHIP;
 }
 

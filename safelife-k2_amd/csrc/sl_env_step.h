@@ -62,8 +62,9 @@ ResetArgs reset_args(const sl_env_cfg *cfg);
 int obs_args(int vh, int vw, int remove_white, int mode, const int32_t *channels, int nch,
              obs::ObsArgs *a);
 int launch_obs(const sl_env_state &st, const obs::ObsArgs &a, void *out, hipStream_t s);
-// the views of the envs the 128x128 reset-list kernel reset this step
-int launch_obs_reset_list(const sl_env_state &st, const obs::ObsArgs &a, uint16_t *out,
+// the views of the envs the 128x128 reset-list kernel reset this step (packed, or channel
+// views of at most obs::kObsMaxCells cells into a 16-byte aligned array)
+int launch_obs_reset_list(const sl_env_state &st, const obs::ObsArgs &a, void *out,
                           const int64_t *scratch, uint32_t step, hipStream_t s);
 // complete the uint16 board of a state whose boards live in planes and mark them stale
 int demote_planes(sl_env_state *st, hipStream_t s);

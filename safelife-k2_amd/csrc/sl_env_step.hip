@@ -110,7 +110,7 @@ int sl::plan_step(const sl_env_state &st, const sl_level_pool *pool, const sl_en
     if (small && st.B > 0x7FFFFFFF) return SL_EINVAL;
 
     // Views.  The 128x128 kernel writes packed views of at most kViewMaxRows128 rows from
-    // the board planes; the 64x64 kernels write packed views, and channel views of up
+    // the board planes (channel views: below); the 64x64 kernels write packed views, and channel views of up
     // to kFusedChanCells cells into a 16-byte aligned array (one wave writes its env's
     // 16-byte chunks from the view masks it builds in LDS); everything else is the
     // observation kernel's, after the resets.
@@ -119,8 +119,16 @@ int sl::plan_step(const sl_env_state &st, const sl_level_pool *pool, const sl_en
     // a board stays in planes over a step without capture whose draws the plane kernels
     // know (128x128 replay: with draw planes, the decided form; 64x64: Philox only)
     const bool planes_can = !p.cap && cfg.board_mode != SL_BOARD_UINT16;
+    // ... and, asked to (SL_OBS_FUSE_CHAN128), channel views of at most
+    // SL_FUSE_CHAN128_MAX_CELLS cells into a 16-byte aligned array: the limits of the wave
+    // writer that gives the reset envs their views (launch_obs_reset_list)
+    static_assert(SL_FUSE_CHAN128_MAX_CELLS <= obs::kObsMaxCells, "the reset envs' writer");
+    const bool chan128 = (cfg.obs_fuse & SL_OBS_FUSE_CHAN128) && p.oa.mode != SL_OBS_PACKED &&
+                         p.oa.vh * p.oa.vw <= SL_FUSE_CHAN128_MAX_CELLS &&
+                         (((uintptr_t)cfg.obs_out) & 15) == 0;
     const bool fuse128 = fast128 && planes128 && planes_can && cfg.obs_out &&
-                         (!replay || st.elig_planes) && p.oa.mode == SL_OBS_PACKED &&
+                         (!replay || st.elig_planes) &&
+                         (p.oa.mode == SL_OBS_PACKED || chan128) &&
                          p.oa.vh <= kViewMaxRows128 && p.oa.vw <= 128;
     const bool fuse64 =
         fast && cfg.obs_out &&

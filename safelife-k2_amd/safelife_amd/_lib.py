@@ -36,6 +36,9 @@ SL_EMD_DEVICE_MAX_CELLS = 256
 SL_EMD_ST_BADCELL, SL_EMD_ST_TOOBIG, SL_EMD_ST_PIVOTS = -1, -2, -3
 SL_BOARD_AUTO, SL_BOARD_UINT16 = 0, 1
 SL_PLANES64_W6_UNSPLIT = -6
+# sl_env_cfg.obs_fuse bits, and the channel-view cell limit of the 128x128 step kernel
+SL_OBS_FUSE_CHAN128 = 1
+SL_FUSE_CHAN128_MAX_CELLS = 4096
 SL_MAX_EXITS = 8
 SL_BONUS_PERIOD_MAX = 16
 SL_OBS_NONE, SL_OBS_PACKED, SL_OBS_CHANNELS, SL_OBS_CHANNELS_U8 = 0, 1, 2, 3
@@ -93,7 +96,7 @@ class EnvCfg(ctypes.Structure):
                 ("obs_out", vp), ("obs_mode", i32), ("obs_vh", i32), ("obs_vw", i32),
                 ("obs_remove_white", i32), ("obs_nch", i32), ("obs_channels", i32 * 16),
                 ("capture", vp), ("stream_phase", i32), ("stream_base", vp), ("mt", vp),
-                ("board_mode", i32), ("planes64_waves", i32)]
+                ("board_mode", i32), ("planes64_waves", i32), ("obs_fuse", i32)]
 
 
 class StepPlan(ctypes.Structure):

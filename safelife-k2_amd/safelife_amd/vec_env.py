@@ -155,7 +155,8 @@ class SafeLifeVecEnv:
                  level_order="sequential", augment_roll=False, env0=0, n_total_envs=None,
                  can_toggle_powers=False, can_toggle_colors=False, obs_dtype="uint16",
                  compute_obs=True, global_counter=None, kernel="auto", stream_exchange=None,
-                 stream_ring="auto", board_mode="auto", planes64_waves=6):
+                 stream_ring="auto", board_mode="auto", planes64_waves=6,
+                 fuse_channel_views128=False):
         import torch
         self.torch = torch
         self.device = _lib.require_device(device)
@@ -215,6 +216,12 @@ class SafeLifeVecEnv:
         if planes64_waves not in (5, 6, _lib.SL_PLANES64_W6_UNSPLIT):
             raise ValueError("planes64_waves must be 5, 6 or -6")
         self.planes64_waves = planes64_waves
+        # 128x128 with output_channels=(...): True has the step kernel write the channel
+        # views from the board planes too (sl_env_cfg.obs_fuse, SL_OBS_FUSE_CHAN128), so the
+        # board stays in planes as it does with packed views -- for views of at most 96
+        # rows and 4096 cells; others, and every other board size, step as with False
+        # (the default: the observation kernel after a step on the uint16 board)
+        self.fuse_channel_views128 = bool(fuse_channel_views128)
         self._board_read_at = None   # step index of the last `board` read
         self._step_index = 0
         # step index and auto_reset flag of the last launched step: the 64x64 and
@@ -633,6 +640,7 @@ class SafeLifeVecEnv:
         c.kernel = self.kernel
         c.board_mode = _lib.SL_BOARD_UINT16 if self._wants_uint16_board() else _lib.SL_BOARD_AUTO
         c.planes64_waves = self.planes64_waves
+        c.obs_fuse = _lib.SL_OBS_FUSE_CHAN128 if self.fuse_channel_views128 else 0
         return c
 
     BOARD_READ_WINDOW = 4
