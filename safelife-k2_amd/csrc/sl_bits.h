@@ -750,6 +750,13 @@ __device__ __forceinline__ RecFields rec_fields(const StepArgs &a, u32 V, int go
     return fl;
 }
 
+// the same distance alone, for a kernel that hands it over instead of reading the table
+// (all scalar; with a bonus only)
+__device__ __forceinline__ int rec_bonus_dist(const StepArgs &a, const RecFields &fl) {
+    return bonus_dist(fl.ax, fl.ay, fl.prior_x(fl.prior_head()), fl.prior_y(fl.prior_head()),
+                      fl.prior_len(), a.bonus_period, a.bonus_len);
+}
+
 // Wave totals of the per-lane sums of score_planes, packed two per reduction (per-lane
 // ranges: points [-192, 320], score [-64, 64], possible and side effects [0, 64], so
 // each total fits 16 bits).  A caller without side effects (wave_reset) passes 0.
@@ -790,31 +797,48 @@ __device__ __forceinline__ void queue_reset(int64_t *scratch, int64_t B, uint32_
 // kernel that runs the epilogue one lane per env (k_env_epilogue_reset64, sl_bits.hip):
 // what epilogue_core takes from the step's wave and cannot re-read from the state arrays.
 // 32 B per env in the scratch words [4B, 8B) (Scratch.act: unused by a Philox plane step),
-// written and read as two 16-byte words.
+// written as two 16-byte words, of which the tail reads the first 24 bytes.  game_over, the
+// agent (64x64: 6 bits each) and the bonus distance share one dword: bit 0, bits 1-6, 7-12
+// and 13-31, so the distance is below kHandDistMax (bonus_dist clamps it to bonus_len - 1;
+// plan_step takes the split pair only with a table that short).
 struct Handover {
     int act_reward, points, score, possible, side;   // the action's reward, the new totals
     int go, ax, ay;                                  // game_over and the agent after the action
+    int dist;                                        // the movement-bonus distance (0: no bonus)
 };
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ i32x4 *handover_of(int64_t *scratch, int64_t B) {
     return reinterpret_cast<i32x4 *>(scratch + 4 * B);
 }
 __device__ __forceinline__ void put_handover(i32x4 *hv, int64_t b, const Handover &h) {
     hv[2 * b] = i32x4{h.act_reward, h.points, h.score, h.possible};
-    hv[2 * b + 1] = i32x4{h.side, h.go, h.ax, h.ay};
+    hv[2 * b + 1] = i32x4{h.side, (int)((u32)h.go | ((u32)h.ax << 1) | ((u32)h.ay << 7) |
+                                        ((u32)h.dist << 13)), 0, 0};
 }
 __device__ __forceinline__ Handover get_handover(const i32x4 *hv, int64_t b) {
-    const i32x4 u = hv[2 * b], v = hv[2 * b + 1];
-    return Handover{u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+    const i32x4 u = hv[2 * b];
+    const i32x2 v = *reinterpret_cast<const i32x2 *>(hv + 2 * b + 1);
+    const u32 w = (u32)v.y;
+    return Handover{u.x, u.y, u.z, u.w, v.x, (int)(w & 1u), (int)((w >> 1) & 63u),
+                    (int)((w >> 7) & 63u), (int)(w >> 13)};
 }
 
 // the epilogue's view in that kernel: the env's fields from the state arrays (one lane per
-// env: the reads coalesce), game_over and the agent from the hand-over record
+// env: the reads coalesce); game_over, the agent and the bonus distance from the hand-over
+// record.  No exits: the step wave has recoloured them in the planes, where the board lives
+// (SL_POK_BOARD_PLANES: k_board_sync64 completes the uint16 board from them, and a reset
+// rewrites it whole).  No ring entry: the distance epilogue_core works out from these is
+// dead, the table entry is the record's.
 struct HandFields : GlobalFields {
-    int go, ax, ay;
+    int go, ax, ay, dist;
+    __device__ int exit_count() const { return 0; }
     __device__ int game_over() const { return go; }
     __device__ int agent_x() const { return ax; }
     __device__ int agent_y() const { return ay; }
+    __device__ int prior_x(int) const { return ax; }
+    __device__ int prior_y(int) const { return ay; }
+    __device__ double bonus(int) const { return bonus_table[dist]; }
 };
 
 }  // namespace bits

@@ -1163,7 +1163,7 @@ k_env_epilogue_reset64(sl_env_state st, StepArgs a, sl_level_pool pool, ResetArg
     bool reset = false;
     if (b < st.B) {
         const Handover h = get_handover(handover_of(scratch, st.B), b);
-        const HandFields f{{st, b, a.bonus_table}, h.go, h.ax, h.ay};
+        const HandFields f{{st, b, a.bonus_table}, h.go, h.ax, h.ay, h.dist};
         reset = epilogue_core(st, a, b, f, h.act_reward, h.points, h.score, h.possible, h.side,
                               reward_out, done_out, flags_out, ep_len_out, ep_rew_out);
     }
@@ -1173,10 +1173,11 @@ k_env_epilogue_reset64(sl_env_state st, StepArgs a, sl_level_pool pool, ResetArg
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t mine = __ballot(reset);
     if (lane == 0) finished[wave] = mine;
-    // the epilogue's stores before the resets' to the same words (the env's scalars, its
-    // exit cells), which other lanes -- of any wave of the block -- issue: retired at
-    // workgroup scope (the block's waves store through one CU to one L2; a device-scope
-    // fence in every wave, with its L2 write-back, cost more than the step kernel gained)
+    // the epilogue's stores before the resets' to the same words (the env's scalars; no
+    // board cell: HandFields has no exits), which other lanes -- of any wave of the block --
+    // issue: retired at workgroup scope (the block's waves store through one CU to one L2; a
+    // device-scope fence in every wave, with its L2 write-back, cost more than the step
+    // kernel gained)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     const int64_t b0 = (int64_t)blockIdx.x * kTailThreads;

@@ -26,6 +26,9 @@ __host__ __device__ inline Scratch scratch_of(int64_t *s, int64_t B) {
     return Scratch{s, s + 2 * B, s + 4 * B, s + 8 * B};
 }
 __host__ __device__ inline int32_t *reset_list(int64_t *s) { return reinterpret_cast<int32_t *>(s); }
+// the hand-over record carries the movement-bonus distance in 19 bits (sl_bits.h Handover):
+// the longest bonus table the split pair steps with (vec_env's has H + W + period + 2 entries)
+constexpr int kHandDistMax = 1 << 19;
 
 // the board planes a cell's spawn eligibility reads (alive, frozen, inhibiting,
 // spawning): what the 128x128 replay paths evaluate eligibility from

@@ -167,7 +167,8 @@ int sl::plan_step(const sl_env_state &st, const sl_level_pool *pool, const sl_en
         else if (!gray) p.kernel64 = SL_PLAN_K64_PLANES;
         else if (p.view_kind || cfg.planes64_waves == 5) p.kernel64 = SL_PLAN_K64_GRAY;
         else if (cfg.planes64_waves != SL_PLANES64_W6_UNSPLIT && cfg.auto_reset &&
-                 (reinterpret_cast<uintptr_t>(cfg.scratch) & 15) == 0)
+                 (reinterpret_cast<uintptr_t>(cfg.scratch) & 15) == 0 &&
+                 (cfg.bonus_period == 0 || cfg.bonus_len <= kHandDistMax))
             p.kernel64 = SL_PLAN_K64_S6;
         else p.kernel64 = SL_PLAN_K64_W6;
     }

@@ -210,7 +210,10 @@
         // the agent planes are rebuilt from the agent's new position below
         eval[k] &= ~ps.agent16();
     }
-    const RecFields fl = rec_fields(a, V, go1, ax1, ay1);
+    // (SPLIT_EPI: the tail kernel reads the bonus table, at the distance handed over)
+    const RecFields fl = SPLIT_EPI ? RecFields{V, go1, ax1, ay1, 0.0}
+                                   : rec_fields(a, V, go1, ax1, ay1);
+    const int hand_dist = SPLIT_EPI && a.bonus_period > 0 ? rec_bonus_dist(a, fl) : 0;
 
     u32 PB[32];
 #pragma unroll
@@ -361,11 +364,12 @@
     }
     if (SPLIT_EPI) {
         // the epilogue runs in k_env_epilogue_reset64, one lane per env: what it cannot
-        // re-read from the state arrays goes out in the env's hand-over record
+        // re-read from the state arrays goes out in the env's hand-over record, and with it
+        // the bonus distance, which the wave has the whole ring for
         if (lane == 0)
             put_handover(handover_of(fx.scratch, st.B), b,
                          Handover{act_reward, tot.points, tot.score, tot.possible, tot.side,
-                                  fl.go, fl.ax, fl.ay});
+                                  fl.go, fl.ax, fl.ay, hand_dist});
     } else {
     int reset = 0;
     if (lane == 0)
