@@ -75,6 +75,14 @@ extern "C" {
                                 aside: Philox draws; SL_ETOOBIG elsewhere.
                                 Accepted by sl_side_effect_densities_k only
                                 (sl_env_cfg.kernel: SL_EINVAL)                */
+#define SL_KERNEL_WIDE 5     /* the bit-sliced step kernel for boards of up to
+                                128 x 128 with more than 64 rows or more than 64
+                                columns, 128x128 aside (80x80, 96x96, 40x128):
+                                Philox draws; SL_ETOOBIG for every other shape
+                                and for SL_RNG_STREAM.  Opt-in: AUTO and FAST
+                                never pick it.  Accepted by sl_env_cfg.kernel
+                                and sl_env_step_family only (the side-effect
+                                rollouts: SL_EINVAL)                          */
 
 /* the step kernel families of sl_env_step (sl_env_step_family) */
 #define SL_FAMILY_GENERIC 0     /* k_env_action + the per-cell kernel, any shape      */
@@ -83,6 +91,9 @@ extern "C" {
 #define SL_FAMILY_MID 3         /* bit-sliced, 33 <= H <= 64, W <= 64, 64x64 aside    */
 #define SL_FAMILY_BITS64 4      /* bit-sliced 64x64 kernels                           */
 #define SL_FAMILY_BITS128 5     /* bit-sliced 128x128 kernels                         */
+#define SL_FAMILY_WIDE 6        /* bit-sliced, H <= 128, W <= 128, H > 64 or W > 64,
+                                   128x128 aside: k_env_action + k_env_step_wide; only
+                                   under SL_KERNEL_WIDE                               */
 
 /* bits of the replay stream's error flag (scratch word 8B, sl_env_cfg.scratch) */
 #define SL_STREAM_ERR_RANGE 1      /* the supplied stream ran out, or the device
@@ -854,7 +865,9 @@ int sl_env_step(sl_env_state *st, const sl_level_pool *pool, const int32_t *acti
 /* which step kernel family sl_env_step runs for this shape and request:
    SL_FAMILY_GENERIC, _SMALL_SEG4, _SMALL, _MID, _BITS64, _BITS128; SL_ETOOBIG where
    kernel == SL_KERNEL_FAST and no bit-sliced kernel takes H x W; SL_EINVAL otherwise bad
-   (host only; no GPU needed).  sl_env_step takes its kernel from this very function; a
+   (host only; no GPU needed).  kernel == SL_KERNEL_WIDE: SL_FAMILY_WIDE where 2 <= H <= 128,
+   2 <= W <= 128, H > 64 or W > 64 and not 128x128, SL_ETOOBIG for every other shape with
+   H, W >= 1; no other request answers SL_FAMILY_WIDE.  sl_env_step takes its kernel from this very function; a
    128x128 state without the goals mirror (sl_env_state.planes) goes to the generic kernel
    under SL_KERNEL_AUTO and is SL_ETOOBIG under SL_KERNEL_FAST all the same. */
 int sl_env_step_family(int H, int W, int kernel);

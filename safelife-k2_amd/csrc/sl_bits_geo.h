@@ -2,8 +2,9 @@
 // than one file uses: Geo64 (64x64 boards: sl_bits.hip, sl_rollout_bits.hip), GeoSmall
 // (boards up to 32 rows x 64 columns: sl_bits_small.hip, sl_rollout_bits.hip), GeoMid
 // (33 to 64 rows, up to 64 columns: sl_bits_mid.hip; here so that the side-effect rollout
-// can take it) and GeoBand with its HaloView (128x128 boards in bands of 32 rows:
-// sl_bits128.hip, sl_rollout_bits128.hip).
+// can take it), GeoBand with its HaloView (128x128 boards in bands of 32 rows:
+// sl_bits128.hip, sl_rollout_bits128.hip) and GeoWide (bands of 32 rows of any board of up
+// to 128 x 128: sl_bits_wide.hip).
 #pragma once
 #include "sl_bits.h"
 
@@ -244,6 +245,69 @@ struct GeoBand {
         }
     }
 };
+
+// Boards of up to 128 x 128 that no other layout takes (more than 64 rows or more than 64
+// columns, 128x128 aside: sl_bits_wide.hip): GeoBand's bands of 32 rows with GeoSmall's
+// columns.  Lane j < nl = ceil(W / 2) holds the column pair (2j, 2j+1) of the band's rows;
+// columns come through ds_bpermute from lanes j -+ 1 modulo nl, and for odd W the last
+// pair's word 1 is a copy of column 0 (at nl = 64 the permute is GeoBand's whole-wave
+// rotation).  The rows just outside the band come from the halo, wrapping at H: the last
+// band holds n = H - 32 (NB - 1) real rows (mh), its other bits hold no cell and every
+// neighbour word is masked, and its lower halo -- row 0 -- enters below row n - 1 (sd), not
+// below bit 31.  Philox draws only (replay is open: DESIGN.md 10).
+template <int MODE>
+struct GeoWide {
+    static_assert(MODE == SPAWN_PHILOX, "GeoWide draws with Philox only");
+    int lane, nl, row0;      // row0: the band's first row
+    u32 mh;                  // the band's real rows
+    int sd;                  // the band's last real row: the lower halo lies below it
+    int src_l, src_r;        // lanes holding columns 2j - 1 and 2j + 2
+    bool odd_last;           // this lane's word 1 is the column-0 copy (odd W)
+    HaloView hv;
+    template <class F>
+    __device__ __forceinline__ V3 vert(const u32 *P, int w, F f) const {
+        const u32 x = f(P, w), o = f(hv, w);
+        return V3{__builtin_amdgcn_alignbit(x, o, 31u) & mh, ((x >> 1) | ((o & 1u) << sd)) & mh};
+    }
+    __device__ __forceinline__ H3 horiz(u32 w0, u32 w1) const {
+        const u32 right_col = odd_last ? w0 : w1;          // this lane's last real column
+        return H3{(u32)__builtin_amdgcn_ds_bpermute(4 * src_l, (int)right_col),
+                  (u32)__builtin_amdgcn_ds_bpermute(4 * src_r, (int)w0)};
+    }
+    __device__ __forceinline__ bool halo_spawn() const {
+        return (PL(hv, 7, 0) | PL(hv, 7, 1)) != 0u;
+    }
+    // the 2x2 spawn block of band rows y, y + 1 (y even) of the lane's column pair
+    __device__ __forceinline__ u32 block(int y) const {
+        return (u32)(((row0 + y) >> 1) * nl + lane);
+    }
+    // only real cells draw: no row past H - 1, nothing in the column-0 copy; lanes past
+    // the board hold zeros
+    __device__ __forceinline__ void spawn(const u32 elig[2], u32 sp[2], const SpawnCtx &sc,
+                                          u32 tensor) {
+        const u32 e[2] = {elig[0] & mh, odd_last ? 0u : elig[1] & mh};
+        philox_spawn(*this, e, sp, sc, tensor);
+    }
+};
+
+// the geometry of lane `lane` in the band of rows row0 .. row0 + 31 of an H x W board
+// (lanes >= ceil(W / 2) hold nothing); the caller sets the halo
+template <int MODE>
+__device__ __forceinline__ GeoWide<MODE> wide_geo(int lane, int H, int W, int row0) {
+    GeoWide<MODE> g;
+    const int nl = (W + 1) >> 1, n = min(32, H - row0);
+    const bool active = lane < nl;
+    g.lane = lane;
+    g.nl = nl;
+    g.row0 = row0;
+    g.mh = n == 32 ? ~0u : ((1u << n) - 1u);
+    g.sd = n - 1;
+    g.src_l = active ? (lane == 0 ? nl - 1 : lane - 1) : lane;
+    g.src_r = active ? (lane + 1 == nl ? 0 : lane + 1) : lane;
+    g.odd_last = (W & 1) && lane == nl - 1;
+    g.hv = HaloView{0u, 0u};
+    return g;
+}
 
 }  // namespace bits
 }  // namespace sl

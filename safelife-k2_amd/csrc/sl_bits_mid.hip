@@ -34,35 +34,7 @@ constexpr int kMinH = 33, kMaxH = 64, kMaxW = 64;
 #define SL_MID_MINW 3        // waves per SIMD the register budget is sized for
 #endif
 
-// The lane's dwords D[y] = cell(row0 + y, c0) | cell(row0 + y, c1) << 16 of a tensor in
-// HBM (t: the env's cells, row stride W).  c1 = c0 + 1, or 0 for the column-0 copy of an
-// odd board.  Even W with t on a dword boundary: one load a row.  No load is predicated
-// (32 predicates would cost the kernel its scalar registers): rows past the board
-// repeat its last row and lanes past it read column pair 0, and the caller clears
-// what is no cell once the rows are planes (mask_planes).
-__device__ __forceinline__ void hbm_rows(const uint16_t *__restrict__ t, int H, int W,
-                                         bool active, int row0, int c0, int c1, u32 D[32]) {
-    const int last = min(32, H - row0) - 1;            // this half's last real row, >= 0
-    const int a0 = active ? c0 : 0, a1 = active ? c1 : 0;
-    if (!(W & 1) && !((uintptr_t)t & 3)) {
-        const u32 *p = reinterpret_cast<const u32 *>(t + row0 * W + a0);
-        const int s = W >> 1;
-#pragma unroll
-        for (int y = 0; y < 32; y++) D[y] = p[min(y, last) * s];
-    } else {
-        const uint16_t *p = t + row0 * W;
-#pragma unroll
-        for (int y = 0; y < 32; y++) {
-            const int r = min(y, last) * W;
-            D[y] = (u32)p[r + a0] | ((u32)p[r + a1] << 16);
-        }
-    }
-}
-// both words of every plane to the lane's real rows (m = 0 for a lane past the board)
-__device__ __forceinline__ void mask_planes(u32 P[32], u32 m) {
-#pragma unroll
-    for (int k = 0; k < 32; k++) P[k] &= m;
-}
+// (the row loads from HBM, hbm_rows, and mask_planes: sl_bits_small.h)
 
 // Per-half OR of a row mask: the rows (bit y = row 32h + y) any lane of this lane's
 // parity has set -- quad xor 2, then two row rotations keep the parity.  lo: rows 0-31,

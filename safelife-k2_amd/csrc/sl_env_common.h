@@ -382,6 +382,10 @@ bool small_seg4_shape(int H, int W);
 // (sl_bits_mid.hip); auto-reset in both: envs whose episode ended are reset by their
 // own wave from the pool
 bool mid_shape(int H, int W);
+// the opt-in bit-sliced kernel for the boards of up to 128 x 128 none of the above takes:
+// more than 64 rows or more than 64 columns, 128x128 aside (sl_bits_wide.hip,
+// SL_KERNEL_WIDE); k_env_action before it, k_env_reset_scan after it
+bool wide_shape(int H, int W);
 // the action of every env (k_env_action, one lane per env): state and cell edits in
 // HBM, reward into act[b]; the 128x128 kernel's pre-pass (sl_env.hip)
 // 128x128 board planes (sl_env_state.board_planes): complete the uint16 board of envs

@@ -49,6 +49,7 @@ const StepHooks &hooks_small();     // sl_bits_small.hip (both small families)
 const StepHooks &hooks_mid();       // sl_bits_mid.hip
 const StepHooks &hooks_64();        // sl_bits.hip
 const StepHooks &hooks_128();       // sl_bits128.hip
+const StepHooks &hooks_wide();      // sl_bits_wide.hip
 
 // k_env_reset_scan over all envs: SL_PLAN_RESETS_SCAN (sl_env.hip)
 int reset_scan(const StepCall &c);

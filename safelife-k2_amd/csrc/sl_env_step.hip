@@ -1,6 +1,6 @@
 // sl_env_step.hip -- sl_env_step: decide, then do.  Host code only; the kernels live
 // with their families (sl_env.hip, sl_bits_small.hip, sl_bits_mid.hip, sl_bits.hip,
-// sl_bits128.hip) and are reached through each family's StepHooks (sl_env_step.h).
+// sl_bits128.hip, sl_bits_wide.hip) and are reached through each family's StepHooks (sl_env_step.h).
 //
 //   plan_step   every decision of a step as a pure function of (state, pool, cfg,
 //               info_flags): the kernel family, replay and its phase, plane mode and
@@ -43,6 +43,8 @@ int view_kind_of(int obs_mode) {
 
 extern "C" int sl_env_step_family(int H, int W, int kernel) {
     if (H < 1 || W < 1) return SL_EINVAL;
+    // opt-in: the one request that answers SL_FAMILY_WIDE, and nothing else
+    if (kernel == SL_KERNEL_WIDE) return wide_shape(H, W) ? SL_FAMILY_WIDE : SL_ETOOBIG;
     if (kernel != SL_KERNEL_AUTO && kernel != SL_KERNEL_GENERIC && kernel != SL_KERNEL_FAST)
         return SL_EINVAL;
     if (kernel != SL_KERNEL_GENERIC) {
@@ -89,6 +91,8 @@ int sl::plan_step(const sl_env_state &st, const sl_level_pool *pool, const sl_en
         if (cfg.kernel == SL_KERNEL_FAST) return SL_ETOOBIG;
         p.family = SL_FAMILY_GENERIC;
     }
+    // (the wide kernel draws with Philox only: replay is open)
+    if (p.family == SL_FAMILY_WIDE && replay) return SL_ETOOBIG;
     const bool fast = p.family == SL_FAMILY_BITS64, fast128 = p.family == SL_FAMILY_BITS128;
     // every one-wave kernel with the uint16 board in HBM, which resets its own finished envs
     const bool small = p.family == SL_FAMILY_MID || p.family == SL_FAMILY_SMALL ||
@@ -107,7 +111,7 @@ int sl::plan_step(const sl_env_state &st, const sl_level_pool *pool, const sl_en
     if (cfg.planes64_waves != 0 && cfg.planes64_waves != 5 && cfg.planes64_waves != 6 &&
         cfg.planes64_waves != SL_PLANES64_W6_UNSPLIT)
         return SL_EINVAL;
-    if (small && st.B > 0x7FFFFFFF) return SL_EINVAL;
+    if ((small || p.family == SL_FAMILY_WIDE) && st.B > 0x7FFFFFFF) return SL_EINVAL;
 
     // Views.  The 128x128 kernel writes packed views of at most kViewMaxRows128 rows from
     // the board planes (channel views: below); the 64x64 kernels write packed views, and channel views of up
@@ -177,7 +181,8 @@ int sl::plan_step(const sl_env_state &st, const sl_level_pool *pool, const sl_en
     // capture those run in the follow-up scan so the pre-reset frame can be copied first.
     // The 64x64 / 128x128 kernels list the finished envs and a second kernel resets them
     // after that frame, so they keep the list (and its per-parity lengths, which only the
-    // reset-list kernel clears) going through captured steps.
+    // reset-list kernel clears) going through captured steps.  The wide kernel stands in
+    // the generic family's sequence: the scan, with or without a capture.
     p.resets = !cfg.auto_reset                    ? SL_PLAN_RESETS_NONE
                : small                            ? (p.cap ? SL_PLAN_RESETS_SCAN : SL_PLAN_RESETS_IN_KERNEL)
                : p.kernel64 == SL_PLAN_K64_S6     ? SL_PLAN_RESETS_SPLIT_TAIL64
@@ -205,6 +210,7 @@ const StepHooks &hooks_of(int family) {
     case SL_FAMILY_BITS64: return hooks_64();
     case SL_FAMILY_BITS128: return hooks_128();
     case SL_FAMILY_MID: return hooks_mid();
+    case SL_FAMILY_WIDE: return hooks_wide();
     case SL_FAMILY_GENERIC: return hooks_generic();
     default: return hooks_small();
     }

@@ -17,12 +17,13 @@ SL_RNG_STREAM, SL_RNG_PHILOX = 0, 1
 SL_KERNEL_AUTO, SL_KERNEL_GENERIC, SL_KERNEL_FAST = 0, 1, 2
 SL_KERNEL_BANDS = 3     # sl_side_effect_densities_k only: the 128x128 four-wave rollout
 SL_KERNEL_MID = 4       # sl_side_effect_densities_k only: the one-wave rollout of 33 to 64 rows
+SL_KERNEL_WIDE = 5      # sl_env_step only: the step kernel of boards past 64 rows or columns
 # sl_env_step_family: the step kernel family of a board shape and kernel request
 (SL_FAMILY_GENERIC, SL_FAMILY_SMALL_SEG4, SL_FAMILY_SMALL, SL_FAMILY_MID, SL_FAMILY_BITS64,
- SL_FAMILY_BITS128) = range(6)
+ SL_FAMILY_BITS128, SL_FAMILY_WIDE) = range(7)
 FAMILY_NAMES = {SL_FAMILY_GENERIC: "generic", SL_FAMILY_SMALL_SEG4: "small-seg4",
                 SL_FAMILY_SMALL: "small", SL_FAMILY_MID: "mid", SL_FAMILY_BITS64: "bits64",
-                SL_FAMILY_BITS128: "bits128"}
+                SL_FAMILY_BITS128: "bits128", SL_FAMILY_WIDE: "wide"}
 # sl_step_plan (sl_env_step_plan): who writes the views, who resets, the 64x64 instance
 SL_PLAN_OBS_NONE, SL_PLAN_OBS_FUSED64, SL_PLAN_OBS_FUSED128, SL_PLAN_OBS_SEPARATE = range(4)
 (SL_PLAN_RESETS_NONE, SL_PLAN_RESETS_IN_KERNEL, SL_PLAN_RESETS_LIST64,
@@ -244,7 +245,8 @@ def check(rc, what):
 
 def env_step_family(H, W, kernel=SL_KERNEL_AUTO):
     """Name of the step kernel family sl_env_step runs on H x W boards for this kernel
-    request (host only); raises where SL_KERNEL_FAST has no bit-sliced kernel."""
+    request (host only); raises where SL_KERNEL_FAST has no bit-sliced kernel, or
+    SL_KERNEL_WIDE is asked for a shape outside its range."""
     rc = lib().sl_env_step_family(int(H), int(W), int(kernel))
     if rc < 0:
         check(rc, "sl_env_step_family(%d, %d, %d)" % (H, W, kernel))

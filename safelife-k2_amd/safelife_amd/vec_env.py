@@ -184,8 +184,15 @@ class SafeLifeVecEnv:
         self.can_toggle_powers = bool(can_toggle_powers)
         self.can_toggle_colors = bool(can_toggle_colors)
         self.compute_obs = bool(compute_obs)
+        # "wide": the opt-in bit-sliced kernel of boards of up to 128 x 128 with more than
+        # 64 rows or more than 64 columns, 128x128 aside (Philox only); "auto" and "fast"
+        # never pick it.  Another shape, or rng="stream", is the SL_ETOOBIG error
         self.kernel = {"auto": _lib.SL_KERNEL_AUTO, "generic": _lib.SL_KERNEL_GENERIC,
-                       "fast": _lib.SL_KERNEL_FAST}[kernel]
+                       "fast": _lib.SL_KERNEL_FAST, "wide": _lib.SL_KERNEL_WIDE}[kernel]
+        if kernel == "wide":
+            _lib.env_step_family(self.H, self.W, self.kernel)
+            if rng == "stream":
+                _lib.check(_lib.SL_ETOOBIG, "kernel='wide' with rng='stream'")
         self.global_counter = global_counter if global_counter is not None else GlobalCounter()
         # rng="stream" over shards: dist.StreamExchange (or any callable of the same
         # contract) places this shard's draws in the global stream every step
@@ -266,7 +273,7 @@ class SafeLifeVecEnv:
     @property
     def kernel_family(self):
         """Name of the step kernel family this env's steps run (sl_env_step_family):
-        "generic", "small-seg4", "small", "mid", "bits64" or "bits128"."""
+        "generic", "small-seg4", "small", "mid", "bits64", "bits128" or "wide"."""
         return _lib.env_step_family(self.H, self.W, self.kernel)
 
     # ------------------------------------------------------------------ setup
