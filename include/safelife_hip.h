@@ -75,14 +75,15 @@ extern "C" {
                                 aside: Philox draws; SL_ETOOBIG elsewhere.
                                 Accepted by sl_side_effect_densities_k only
                                 (sl_env_cfg.kernel: SL_EINVAL)                */
-#define SL_KERNEL_WIDE 5     /* the bit-sliced step kernel for boards of up to
+#define SL_KERNEL_WIDE 5     /* the bit-sliced step kernel, and the bit-sliced
+                                side-effect rollout, for boards of up to
                                 128 x 128 with more than 64 rows or more than 64
                                 columns, 128x128 aside (80x80, 96x96, 40x128):
                                 Philox draws; SL_ETOOBIG for every other shape
                                 and for SL_RNG_STREAM.  Opt-in: AUTO and FAST
-                                never pick it.  Accepted by sl_env_cfg.kernel
-                                and sl_env_step_family only (the side-effect
-                                rollouts: SL_EINVAL)                          */
+                                never pick it.  Accepted by sl_env_cfg.kernel,
+                                sl_env_step_family and
+                                sl_side_effect_densities_k                    */
 
 /* the step kernel families of sl_env_step (sl_env_step_family) */
 #define SL_FAMILY_GENERIC 0     /* k_env_action + the per-cell kernel, any shape      */
@@ -340,6 +341,14 @@ int sl_side_effect_densities(const uint16_t *init_board, const uint16_t *final_b
  *            four launches per call -- Philox draws on those shapes, read as uint16 (no
  *            alignment rule); SL_ETOOBIG elsewhere, stream mode included.  SL_KERNEL_FAST
  *            keeps its shape set and is SL_ETOOBIG on these boards;
+ *            SL_KERNEL_WIDE: the bit-sliced rollout of boards of up to 128 x 128 with more
+ *            than 64 rows or more than 64 columns, 128x128 aside (the shapes of the wide
+ *            env step), one workgroup of ceil(H / 32) waves per board: a wave per band of
+ *            32 rows, lane j the columns 2j, 2j + 1, the band in registers, one halo row
+ *            each way through LDS per advance, the same four launches per call -- Philox
+ *            draws on those shapes, read as dwords where W is even and the address a
+ *            multiple of 4 and as uint16 otherwise (no alignment rule); SL_ETOOBIG
+ *            elsewhere, stream mode included.  Opt-in: SL_KERNEL_AUTO never picks it;
  *            SL_KERNEL_AUTO: what sl_side_effect_kernel_auto names: FAST where it
  *            exists, BANDS on 128x128 boards with Philox draws, else GENERIC.  On the
  *            MID shapes of at least 32 columns (at least half of the wave's lanes hold

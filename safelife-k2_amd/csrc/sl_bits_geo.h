@@ -290,6 +290,15 @@ struct GeoWide {
     }
 };
 
+// row r of a tensor in HBM as the lane's dword in GeoWide's columns (a0, a1: the lane's
+// columns): one dword where W is even and the tensor's address a multiple of 4, else two
+// uint16 (sl_bits_wide.hip, sl_rollout_bits_wide.hip)
+__device__ __forceinline__ u32 hbm_row(const uint16_t *__restrict__ t, int W, int r, int a0,
+                                       int a1) {
+    if (!(W & 1) && !((uintptr_t)t & 3)) return reinterpret_cast<const u32 *>(t + r * W + a0)[0];
+    return (u32)t[r * W + a0] | ((u32)t[r * W + a1] << 16);
+}
+
 // the geometry of lane `lane` in the band of rows row0 .. row0 + 31 of an H x W board
 // (lanes >= ceil(W / 2) hold nothing); the caller sets the halo
 template <int MODE>

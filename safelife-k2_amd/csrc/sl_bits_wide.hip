@@ -36,13 +36,6 @@ namespace {
 #define SL_WIDE_MINW 3        // waves per SIMD the register budget is sized for
 #endif
 
-// row r of a tensor in HBM as the lane's dword (hbm_rows' forms; a0, a1: the lane's columns)
-__device__ __forceinline__ u32 hbm_row(const uint16_t *__restrict__ t, int W, int r, int a0,
-                                       int a1) {
-    if (!(W & 1) && !((uintptr_t)t & 3)) return reinterpret_cast<const u32 *>(t + r * W + a0)[0];
-    return (u32)t[r * W + a0] | ((u32)t[r * W + a1] << 16);
-}
-
 // the rows of `rows` (wave-uniform, bit y = row row0 + y < H) of the lane's column pair,
 // from the dwords D
 __device__ __forceinline__ void store_rows(uint16_t *t, const u32 D[32], u32 rows, int W,

@@ -520,7 +520,7 @@ extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
                                           int64_t workspace_bytes, const uint32_t *env_ids,
                                           int kernel, void *stream) {
     if (kernel != SL_KERNEL_AUTO && kernel != SL_KERNEL_GENERIC && kernel != SL_KERNEL_FAST &&
-        kernel != SL_KERNEL_BANDS && kernel != SL_KERNEL_MID)
+        kernel != SL_KERNEL_BANDS && kernel != SL_KERNEL_MID && kernel != SL_KERNEL_WIDE)
         return SL_EINVAL;
     if (E < 0 || H < 2 || W < 2 || num_samples < 1 || max_keys < 1 || max_keys > 1024)
         return SL_EINVAL;
@@ -553,6 +553,11 @@ extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
                       (kernel == SL_KERNEL_AUTO &&
                        sl_side_effect_kernel_auto(H, W, rng_mode) == SL_KERNEL_MID));
     if (kernel == SL_KERNEL_MID && !mid) return SL_ETOOBIG;
+    // ... and the band rollout of boards past 64 rows or columns: Philox draws, dword or
+    // uint16 reads as the address allows (no alignment rule); only when asked for
+    const bool wide = kernel == SL_KERNEL_WIDE && rng_mode == SL_RNG_PHILOX &&
+                      rollout_wide_shape(H, W);
+    if (kernel == SL_KERNEL_WIDE && !wide) return SL_ETOOBIG;
     if (((fast && H == 64) || bands) &&
         ((((uintptr_t)init_board) | ((uintptr_t)final_board)) & 3)) {
         if (kernel != SL_KERNEL_AUTO) return SL_EINVAL;
@@ -572,12 +577,13 @@ extern "C" int sl_side_effect_densities_k(const uint16_t *init_board,
         max_steps = num_steps_host[e] > max_steps ? num_steps_host[e] : max_steps;
     }
     const int64_t map_elems = E * (int64_t)max_keys * hw;
-    if (fast || bands || mid) {
+    if (fast || bands || mid || wide) {
         // four launches: mark, compact, count, normalise (sl_rollout_bits.hip,
-        // sl_rollout_bits_mid.hip, sl_rollout_bits128.hip); the mark pass writes every
-        // bitmap word, the boards stay where the caller has them
-        const auto launch_rollout = bands ? launch_rollout_bands
-                                    : mid ? launch_rollout_mid : launch_rollout_bits;
+        // sl_rollout_bits_mid.hip, sl_rollout_bits128.hip, sl_rollout_bits_wide.hip); the
+        // mark pass writes every bitmap word, the boards stay where the caller has them
+        const auto launch_rollout = bands  ? launch_rollout_bands
+                                    : mid  ? launch_rollout_mid
+                                    : wide ? launch_rollout_wide : launch_rollout_bits;
         RolloutArgs ra{init_board, final_board, num_steps_dev, spawn_prob, env_ids, env0, seed,
                        num_samples, H, W, bitmap, keys, n_keys, max_keys, inaction, action};
         if (hipMemsetAsync(inaction, 0, map_elems * 8, s) != hipSuccess ||

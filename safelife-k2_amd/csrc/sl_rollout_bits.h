@@ -1,6 +1,6 @@
 // sl_rollout_bits.h -- launcher of the bit-sliced side-effect rollout kernels
-// (sl_rollout_bits.hip, sl_rollout_bits_mid.hip, sl_rollout_bits128.hip), called by sl_side_effect_densities_k
-// (sl_board.hip).
+// (sl_rollout_bits.hip, sl_rollout_bits_mid.hip, sl_rollout_bits128.hip,
+// sl_rollout_bits_wide.hip), called by sl_side_effect_densities_k (sl_board.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,5 +44,16 @@ bool rollout_mid_shape(int H, int W);
 // the same two passes, one launch of 2E single-wave workgroups each; the boards are read
 // as uint16 (no alignment rule)
 int launch_rollout_mid(const RolloutArgs &a, int64_t E, int pass, hipStream_t s);
+
+// the band rollout of boards past 64 rows or columns (sl_rollout_bits_wide.hip) exists for
+// this shape: wide_shape (sl_bits_wide.hip; declared in sl_env_common.h too) -- 2 <= H, W
+// <= 128, H > 64 or W > 64, not 128x128 -- Philox draws only
+bool wide_shape(int H, int W);
+bool rollout_wide_shape(int H, int W);
+
+// the same two passes, one launch of 2E workgroups of ceil(H / 32) waves each; the boards
+// are read as dwords where W is even and the address a multiple of 4, else as uint16 (no
+// alignment rule)
+int launch_rollout_wide(const RolloutArgs &a, int64_t E, int pass, hipStream_t s);
 
 }  // namespace sl

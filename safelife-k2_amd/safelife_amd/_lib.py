@@ -17,7 +17,8 @@ SL_RNG_STREAM, SL_RNG_PHILOX = 0, 1
 SL_KERNEL_AUTO, SL_KERNEL_GENERIC, SL_KERNEL_FAST = 0, 1, 2
 SL_KERNEL_BANDS = 3     # sl_side_effect_densities_k only: the 128x128 four-wave rollout
 SL_KERNEL_MID = 4       # sl_side_effect_densities_k only: the one-wave rollout of 33 to 64 rows
-SL_KERNEL_WIDE = 5      # sl_env_step only: the step kernel of boards past 64 rows or columns
+SL_KERNEL_WIDE = 5      # boards past 64 rows or columns: sl_env_step's kernel and
+                        # sl_side_effect_densities_k's band rollout (opt-in in both)
 # sl_env_step_family: the step kernel family of a board shape and kernel request
 (SL_FAMILY_GENERIC, SL_FAMILY_SMALL_SEG4, SL_FAMILY_SMALL, SL_FAMILY_MID, SL_FAMILY_BITS64,
  SL_FAMILY_BITS128, SL_FAMILY_WIDE) = range(7)

@@ -67,7 +67,7 @@ def _rollout_device(init_boards, final_boards, num_steps, spawn_prob, num_sample
     mode = {"philox": _lib.SL_RNG_PHILOX, "stream": _lib.SL_RNG_STREAM}[rng]
     kern = {"auto": _lib.SL_KERNEL_AUTO, "generic": _lib.SL_KERNEL_GENERIC,
             "fast": _lib.SL_KERNEL_FAST, "bands": _lib.SL_KERNEL_BANDS,
-            "mid": _lib.SL_KERNEL_MID}[kernel]
+            "mid": _lib.SL_KERNEL_MID, "wide": _lib.SL_KERNEL_WIDE}[kernel]
     ids = None
     if env_ids is not None:
         ids_h = np.ascontiguousarray(np.asarray(env_ids, dtype=np.int64).reshape(-1))
@@ -125,6 +125,9 @@ def side_effect_densities(init_boards, final_boards, num_steps, spawn_prob, num_
     'mid' the bit-sliced rollout of boards of 33 to 64 rows and 2 to 64 columns, 64x64
     aside (one wave per board, the same four launches: Philox draws on those shapes; raises
     elsewhere; 'fast' still raises on them),
+    'wide' the bit-sliced rollout of boards of up to 128 x 128 with more than 64 rows or
+    more than 64 columns, 128x128 aside (a wave per band of 32 rows, the same four launches:
+    Philox draws on those shapes; raises elsewhere; opt-in, 'auto' never takes it),
     'generic' the per-cell kernels (one launch per advance), 'auto' takes 'fast' or 'bands'
     where they exist and 'mid' on its shapes of at least 32 columns
     (``sl_side_effect_kernel_auto`` names the choice; narrower 'mid' shapes stay on
@@ -388,7 +391,7 @@ def side_effect_problems(init_boards, final_boards, num_steps, spawn_prob, num_s
                          **rollout_kw):
     """The inputs of ``side_effect_scores``' EMDs, selected on the device: the rollout of
     ``side_effect_densities`` (``rollout_kw``: rng, seed, env_ids, kernel ('auto', 'generic',
-    'fast', 'bands', 'mid'), max_keys, ...),
+    'fast', 'bands', 'mid', 'wide'), max_keys, ...),
     then per episode and key the cells ``earth_mover_distance`` would keep of the two
     density maps (side_effects.py:36-43) -- |a - b| > 1e-3 * max |a - b|, row-major -- cut
     out by ``sl_side_effect_problem_counts`` / ``_cells``.  Only those cells, their keys
@@ -497,7 +500,7 @@ def side_effect_scores(init_boards, final_boards, num_steps, spawn_prob, num_sam
                        include=None, exclude=None, problems="host", emd="host", **rollout_kw):
     """side_effects.py:95-161 for E finished episodes: one device call for all rollouts
     (``side_effect_densities``; ``rollout_kw`` goes to it: rng, seed, env_ids, kernel
-    ('auto', 'generic', 'fast', 'bands', 'mid'), ...), then the host EMD per episode and
+    ('auto', 'generic', 'fast', 'bands', 'mid', 'wide'), ...), then the host EMD per episode and
     key.
     problems: 'host' copies the dense maps to the host and selects each EMD's cells there
     with numpy; 'device' selects them on the device (``side_effect_problems``), copies only
@@ -538,8 +541,8 @@ def side_effect_score(game, num_samples=1000, include=None, exclude=None, proble
     """side_effects.py:95-161 for one game-like object (``_init_data['board']``,
     ``board``, ``num_steps``, ``spawn_prob``): {key: [emd, sum(inaction density)]}.
     The rollout runs on the GPU (``side_effect_densities``); ``kw`` selects its RNG and
-    its kernel ('auto', 'generic', 'fast', 'bands' for 128x128 boards, or 'mid' for boards
-    of 33 to 64 rows); ``problems``
+    its kernel ('auto', 'generic', 'fast', 'bands' for 128x128 boards, 'mid' for boards
+    of 33 to 64 rows, or 'wide' for other boards past 64 rows or columns); ``problems``
     ('host', 'device') where the EMDs' cells are selected and ``emd`` ('host', 'device')
     where they are solved (``side_effect_scores``).
     The E = 1 case of ``side_effect_scores``."""

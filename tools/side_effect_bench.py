@@ -2,11 +2,13 @@
 """A/B of the side-effect rollout kernels: side_effects.side_effect_densities with
 kernel="generic" (one per-cell launch per advance) against the bit-sliced rollout (four
 launches per call): kernel="fast" (one wave per board), on 128x128 boards kernel="bands"
-(four waves per board), or on boards of 33 to 64 rows kernel="mid" (one wave per board).
+(four waves per board), on boards of 33 to 64 rows kernel="mid" (one wave per board), or on
+other boards past 64 rows or columns kernel="wide" (a wave per band of 32 rows).
 
     python tools/side_effect_bench.py [--out profiles/side_effect_rollout_ab.json]
     python tools/side_effect_bench.py --boards 128 [--out profiles/side_effect_rollout128_ab.json]
     python tools/side_effect_bench.py --boards mid [--out profiles/side_effect_rollout_mid_ab.json]
+    python tools/side_effect_bench.py --boards wide [--out profiles/side_effect_rollout_wide_ab.json]
 
 Default: the C3 pool's 64x64 boards and the C2 pool's 25x25 boards (tests/golden/pools),
 E in {1, 64, 1024} episodes, generic against fast.  --boards 128: the C5 pool's 128x128
@@ -17,6 +19,9 @@ shapes is committed, so the boards are those of tools/mid_bench.py's seeded gene
 (make_levels).  The record also says what kAutoTakesMidRollout (sl_board.hip) follows from
 it: true if at every shape of W >= 32 and every E the slowest mid run beats the fastest
 generic run.
+--boards wide: boards of 96x96, 100x100, 65x128 and 40x128 (the shapes of tools/wide_bench.py,
+from the same generator), E in {1, 64, 256}, generic against wide.  The kernel is opt-in
+whatever the numbers say; the record lists the cases it does not win.
 num_steps = 1000, num_samples = 1000, max_keys = 16 (at 64 the 64x64
 maps of 1024 episodes are 4 GiB).  Three runs of each kernel, interleaved (generic, fast,
 generic, ...); every timed call runs in a child process of its own under a time limit,
@@ -76,13 +81,17 @@ POOLS = {"c3_64x64": "c3_prune_still_64.npz", "c2_25x25": "c2_append_still_25.np
 # generated boards (tools/mid_bench.py: make_levels), by shape
 MID_SHAPES = {"mid_33x32": (33, 32), "mid_48x48": (48, 48), "mid_64x48": (64, 48),
               "mid_33x20": (33, 20)}
+WIDE_SHAPES = {"wide_96x96": (96, 96), "wide_100x100": (100, 100), "wide_65x128": (65, 128),
+               "wide_40x128": (40, 128)}
+GENERATED = dict(MID_SHAPES, **WIDE_SHAPES)
 AUTO_MID_MIN_W = 32         # kAutoMidMinW (sl_board.hip)
 STEPS = SAMPLES = 1000
 MAX_KEYS = 16
 # --boards: the pools, the episode counts, the kernel set against generic, the record
 SETS = {"64": (("c3_64x64", "c2_25x25"), (1, 64, 1024), "fast", "side_effect_rollout_ab.json"),
         "128": (("c5_128x128",), (1, 64, 256), "bands", "side_effect_rollout128_ab.json"),
-        "mid": (tuple(MID_SHAPES), (1, 64, 1024), "mid", "side_effect_rollout_mid_ab.json")}
+        "mid": (tuple(MID_SHAPES), (1, 64, 1024), "mid", "side_effect_rollout_mid_ab.json"),
+        "wide": (tuple(WIDE_SHAPES), (1, 64, 256), "wide", "side_effect_rollout_wide_ab.json")}
 RUNS = 3
 CALL_LIMIT_S = 240
 # --problems: pool, episode counts, what is timed by default
@@ -96,10 +105,10 @@ EMD_RECORD = "side_effect_emd_ab.json"
 
 def _pool_boards(pool):
     import numpy as np
-    if pool in MID_SHAPES:
+    if pool in GENERATED:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         from mid_bench import make_levels
-        return np.stack([d["board"] for d in make_levels(*MID_SHAPES[pool])])
+        return np.stack([d["board"] for d in make_levels(*GENERATED[pool])])
     return np.load(os.path.join(REPO, "tests", "golden", "pools", POOLS[pool]))["board"]
 
 
@@ -412,6 +421,11 @@ def main():
         result["auto_min_w"] = AUTO_MID_MIN_W
         result["auto_takes_mid"] = not lost
         result["auto_cases_lost"] = lost
+    if args.boards == "wide":
+        result["boards"] = "tools/mid_bench.py make_levels(H, W), 32 levels, seed 0"
+        result["opt_in"] = True
+        result["cases_not_won"] = ["%s E=%d" % (c["pool"], c["E"]) for c in result["cases"]
+                                   if not c["wide_wins"]]
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
         json.dump(result, f, indent=1)
